@@ -4,7 +4,12 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`, one process
 per GPU (torch.distributed.run for N > 1).  A *step* is one pass of the hot
 path over one batch of synthetic lookups already resident in HBM.  rank 0
-prints ONE JSON line.
+prints ONE JSON line.  A plain run sets up, warms up, times the K steps and
+prints the line; `--full` then also runs the CPU baseline (the oracle) with its
+parity check, the N > 1 sharded parity check, and fills in the PMC traffic and
+survey-model figures of the roofline.  `--dump-outputs DIR` writes the last
+timed step's per-lookup results as DIR/<field>.npy (inputs are seeded, so two
+builds given the same arguments can be compared output for output).
 
 Workloads (--workload, default C):
   A  Chord, 1000 nodes (nodes_2d_15000.xml coordinates), successorListSize 8,
@@ -96,13 +101,20 @@ def parse():
     ap.add_argument("--routing", choices=["iterative", "semi-recursive"], default="iterative",
                     help="Chord routingType (semi-recursive = omnetpp.ini ChordLarge)")
     ap.add_argument("--seed", type=int, default=None, help="population seed (default: the workload's, 0xC)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline (oracle) with its parity check, the N > 1 "
+                         "sharded parity check, and report the PMC traffic and survey-model figures of the roofline; "
+                         "a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the per-lookup results of the last timed step as DIR/<name>.npy (float64; a fixed "
+                         "seeded sample of the batch when it is larger than the 64 MB limit)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--traffic-json", default=None,
-                    help="PMC summary (tools/pmc_json.py); default profiles/pmc/<workload>.json when present")
+                    help="PMC summary (tools/pmc_json.py); default profiles/pmc/<workload>.json when present (--full)")
     ap.add_argument("--traffic-csv", default=None,
                     help="rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE outputs (counter_collection.csv or run_results.db), "
-                         "comma separated")
+                         "comma separated (--full)")
     return ap.parse_args()
 
 
@@ -327,6 +339,33 @@ def traffic_from_csv(path: str | None, kernel_substr: str):
     return fetch + write
 
 
+# --dump-outputs: the arrays of one run stay under 64 MB (float64 columns); a larger batch is sampled
+# at indices drawn once from DUMP_SEED, so two builds given the same arguments write the same lookups
+DUMP_BUDGET_BYTES = 60_000_000
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(path: str, res: dict, index: np.ndarray, m: int, prefix: str = "", world: int = 1) -> None:
+    """Write the step's per-lookup results `res` (field -> array, one row per lookup; row i is lookup
+    `index[i]` of this rank's batch of m, or lookup i when index is None) as <path>/<prefix><field>.npy
+    in float64 (u32 node indices, counts and int64 ns below 2^53 are exact), with the lookups'
+    batch indices as <prefix>index.npy."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    rows = len(next(iter(res.values())))
+    cols = 1 + sum(int(np.prod(np.asarray(v).shape[1:], dtype=np.int64)) for v in res.values())
+    keep = int(min(m, DUMP_BUDGET_BYTES // world // (8 * cols)))     # the limit holds for all ranks together
+    index = np.arange(rows, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64)
+    if keep < m:
+        sample = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=keep, replace=False))
+        sel = np.flatnonzero(np.isin(index, sample))
+    else:
+        sel = np.arange(rows, dtype=np.int64)
+    np.save(out / f"{prefix}index.npy", index[sel].astype(np.float64))
+    for f, v in res.items():
+        np.save(out / f"{prefix}{f}.npy", np.ascontiguousarray(np.asarray(v)[sel]).astype(np.float64))
+
+
 def main():
     a = parse()
     import torch
@@ -468,13 +507,13 @@ def main():
 
     # ---- work of one step (identical every step: same inputs)
     rpc_total = None
-    gres = None          # the last step's per-lookup results, in batch order (for the parity check)
+    gres = None          # the last step's per-lookup results, in batch order (parity check, --dump-outputs)
     if sharded:
         hop_total, n_ok = sh.hop_total(), sh.ok_total()
         kern_ms = sh.kernel_ms / max(sh.runs, 1)
         if kind == "kademlia":
             rpc_total = sh.rpc_total()     # FindNodeCalls of this rank's lookups (done records)
-        if world == 1:
+        if world == 1 and (a.full or a.dump_outputs):
             gres = sh.results_by_qid()
     else:
         outs = dout.cpu().numpy().reshape(-1, 16)
@@ -486,12 +525,30 @@ def main():
             rpcs_np = drpc.cpu().numpy().view(np.uint32)
             rpc_total = int(rpcs_np.astype(np.int64).sum())
             gres["rpcs"] = rpcs_np
-        if refresh:
+        if refresh and (a.full or a.dump_outputs):
             gres["siblings"] = dsib.cpu().numpy().view(np.uint32)
         kern_ms = step_ms
 
+    if a.dump_outputs:
+        wd.set("dump outputs", 300)
+        pre = f"rank{rank}_" if world > 1 else ""
+        if gres is not None:
+            dump_outputs(a.dump_outputs, gres, None, m, pre, world)
+        else:
+            # N > 1 sharded: a lookup's record lives on the rank where it finished; every rank writes
+            # the records it holds, in qid order (qid = home rank x m + index in the home rank's batch)
+            from oversim_amd.shard import done_to_numpy
+            d = done_to_numpy(sh._done)
+            d = d[np.argsort(d["qid"], kind="stable")]
+            held = {f: d[f] for f in ROUTE_FIELDS}
+            held["qid"] = d["qid"]
+            if kind == "kademlia":
+                held["rpcs"] = d["pad"]
+            dump_outputs(a.dump_outputs, held, d["qid"].astype(np.int64) % m, m, pre, world)
+        wd.set("results", 300)
+
     sparity = None
-    if sharded and world > 1 and os.environ.get("OVS_BENCH_PARITY", "1") != "0":
+    if a.full and sharded and world > 1 and os.environ.get("OVS_BENCH_PARITY", "1") != "0":
         wd.set("sharded parity check (oracle)", 900)
         sample = int(os.environ.get("OVS_BENCH_PARITY_SAMPLE", PARITY_SAMPLE.get(a.workload, 20_000)))
         sparity = sharded_parity(sh, kind, ids_np, xy_np, dkeys, dsrc, m, world,
@@ -522,13 +579,15 @@ def main():
             per_launch_bytes = rpc_total * B_RPC + lookups_launch * B_KLOOKUP
             bper = f"{B_RPC} B/RPC + {B_KLOOKUP} B/lookup"
         achieved = per_launch_bytes / (kern_ms * 1e-3) / 1e9
-        traffic, traffic_src = (traffic_from_json(a.traffic_json, a.workload, kname) if world == 1 and not sharded
-                                else (None, None))
-        if a.traffic_csv:
+        # a plain run reports what its own timed steps give; the committed PMC summaries, the survey
+        # model, the CPU baseline and the parity checks belong to --full
+        traffic, traffic_src = (traffic_from_json(a.traffic_json, a.workload, kname)
+                                if a.full and world == 1 and not sharded else (None, None))
+        if a.full and a.traffic_csv:
             traffic, traffic_src = traffic_from_csv(a.traffic_csv, kname), a.traffic_csv
         cpu = None
         parity = sparity
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             wd.set("cpu baseline", 900)
             if ids is None:       # device-generated population (D, E): the oracle needs host copies
                 ids, xy = ids_t.cpu().numpy().view(np.uint32), xy_t.cpu().numpy()
@@ -603,7 +662,7 @@ def main():
                 "gather_ceiling_GBs": GATHER_CEILING_GBS,
                 "frac_of_gather_ceiling": achieved / GATHER_CEILING_GBS,
                 **({"survey_model": survey_model(kind, hop_total, rpc_total, lookups_launch, kern_ms)}
-                   if kind in ("chord", "kademlia") else {}),
+                   if a.full and kind in ("chord", "kademlia") else {}),
             },
             "cpu_baseline": cpu,
             "parity": parity,

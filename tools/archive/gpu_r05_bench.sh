@@ -9,7 +9,7 @@ for w in "$@"; do
     timeout -k 10 300 python3 -u tools/diag/rccl_big.py ${RCCL_ARGS:-} > $O/rccl.out 2> $O/rccl.err || { tail -20 $O/rccl.err; exit 1; }
     cat $O/rccl.out
   else
-    timeout -k 10 600 python3 -u bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
+    timeout -k 10 600 python3 -u bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
     cut -c1-1500 $O/bench_$w.json
   fi
 done

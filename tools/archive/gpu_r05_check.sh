@@ -15,6 +15,6 @@ if [ "$K" != "none" ]; then
   tail -2 $O/gpu_tests.log
 fi
 for w in "$@"; do
-  timeout -k 10 300 python -u bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
   cat $O/bench_$w.json
 done

@@ -13,7 +13,7 @@ if [ $MODE = tests ]; then
   tail -3 $O/smoke.log
 else
   for w in ${*:-C A B D E K R}; do
-    timeout -k 10 600 python3 -u bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
+    timeout -k 10 600 python3 -u bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
     python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); p=d.get('parity') or {}
