@@ -2,9 +2,10 @@
 //
 // The context owns the device routing tables (sorted 24 B node records,
 // fp64 coordinates, CSR finger rows / Kademlia buckets) and one HIP stream.
-// Host-pointer calls stage through context-owned scratch buffers and are
-// synchronous; OVS_DEVICE_PTRS calls launch asynchronously on the caller's
-// stream.  No C++ exception crosses the boundary.
+// Host-pointer calls stage their arrays in per-call device copies (CallFrame,
+// call_frame.hpp), run on the context's stream and are synchronous;
+// OVS_DEVICE_PTRS calls launch asynchronously on the caller's stream.  No C++
+// exception crosses the boundary.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "call_frame.hpp"
 #include "ctx_internal.hpp"
 #include "epichord.hpp"
 #include "host_tables.hpp"
@@ -68,24 +70,11 @@ struct ovs_ctx {
     KoordeTables koorde{};
     // epichord routing snapshot (ovs_epichord_load)
     EpiTables epi{};
-    uint32_t* kvis = nullptr;            // internal visited lists (K3 without hop_seq, K2x without responders)
-    uint64_t kvis_cap = 0;
-    hipEvent_t kvis_ev = nullptr;        // recorded after the last launch that used kvis (kvis_acquire)
-    bool kvis_used = false;
+    CachedBuf kvis;                      // internal visited lists (K3 without hop_seq, K2x without responders)
     // K1's key-order buffers (ksort.hip): sorted keys, sources, caller indices and the sort's
-    // histograms, one allocation shared by the calls on this context like kvis (ks_ev orders them)
-    uint8_t* ks = nullptr;
-    uint64_t ks_cap = 0;
-    hipEvent_t ks_ev = nullptr;
-    bool ks_used = false;
-    // the persistent route kernels' dynamic-tail counters (dyn_acquire): one 64 B slot per launch, a
-    // slot's previous launch ordered before its reuse by an event, so concurrent calls on different
-    // streams never share a counter
-    static constexpr int DYN_SLOTS = 32;
-    unsigned long long* dyn = nullptr;
-    hipEvent_t dyn_ev[DYN_SLOTS] = {};
-    bool dyn_used[DYN_SLOTS] = {};
-    uint32_t dyn_seq = 0;
+    // histograms, one allocation shared by the calls on this context like kvis
+    CachedBuf ks;
+    DynSlots dyn;                        // the persistent route kernels' dynamic-tail counters (dyn_acquire)
     // multi-GPU Kademlia: this rank's in-flight lookups (ovs_kad_shard_begin)
     void* kst = nullptr;                 // KadLookup<alpha> state records
     uint8_t* kact = nullptr;             // 0 never runs, 1 suspended in kst, 2 not started
@@ -103,8 +92,6 @@ struct ovs_ctx {
     int kfcap = 8;                       // findNode capacity of the shard records (8; 16 KademliaLarge)
     int32_t kns = -1;                    // LookupCall batch: numSiblings (-1: KBR routes)
     uint32_t* ksib = nullptr;            // ... and the caller's sibling rows
-    // scratch for host-pointer calls
-    std::vector<void*> scratch;
     // the sharded round loop (shard_route.cpp): cohort streams and cached buffers
     hipStream_t cohort[4] = {nullptr, nullptr, nullptr, nullptr};
     void* route_scratch = nullptr;
@@ -175,10 +162,8 @@ void free_tables(ovs_ctx* c)
     kad_free(c->kad);
     koorde_free(c->koorde);
     epichord_free(c->epi);
-    if (c->kvis) hipFree(c->kvis);      // hipFree waits for the launches that use it
-    c->kvis = nullptr; c->kvis_cap = 0; c->kvis_used = false;
-    if (c->ks) hipFree(c->ks);
-    c->ks = nullptr; c->ks_cap = 0; c->ks_used = false;
+    c->kvis.free();
+    c->ks.free();
     c->overlay = 0; c->n = 0; c->nfing = 0;
     c->bbox_ok = false;
     c->ch.clear();
@@ -197,67 +182,27 @@ void free_kad_shard(ovs_ctx* c)
     c->knlook = 0; c->kcap = 0; c->kalpha = 0;
 }
 
-// The context's cached scratch for internal visited / hop lists (kvis) is one buffer shared by every
-// call on the context.  A call on stream s first waits for the last launch that used it (kvis_ev, on
-// whichever stream that was) and records its own use after its launch (kvis_release), so calls on
-// different streams -- device-pointer calls return while their kernels run -- never rewrite each
-// other's rows.  Growing the buffer waits for that last use only, not for the whole device.
 // A zeroed work counter for one launch of a persistent route kernel (the dynamic tail of K1,
-// launch_chord_route, and K2, kad_route): nullptr when none can be had -- the kernel then runs static slices only.
-static unsigned long long* dyn_acquire(ovs_ctx* c, uint64_t n, hipStream_t s, int* slot)
+// launch_chord_route, and K2, kad_route), released when the lease goes out of scope: get() is
+// nullptr when none can be had -- the kernel then runs static slices only.
+DynSlots::Lease dyn_acquire(ovs_ctx* c, uint64_t n, hipStream_t s)
 {
-    *slot = -1;
-    if (std::getenv("OVS_NO_DYN")) return nullptr;       // A/B: static slices only
-    if (n < (1ull << 18)) return nullptr;                 // small batches: static slices (no memset, no event)
-    if (!c->dyn && hipMalloc(&c->dyn, 64 * ovs_ctx::DYN_SLOTS) != hipSuccess) { c->dyn = nullptr; return nullptr; }
-    const int k = (int)(c->dyn_seq++ % ovs_ctx::DYN_SLOTS);
-    if (!c->dyn_ev[k] && hipEventCreateWithFlags(&c->dyn_ev[k], hipEventDisableTiming) != hipSuccess) {
-        c->dyn_ev[k] = nullptr;
-        return nullptr;
-    }
-    if (c->dyn_used[k] && hipStreamWaitEvent(s, c->dyn_ev[k], 0) != hipSuccess) return nullptr;
-    unsigned long long* p = c->dyn + 8 * k;
-    if (hipMemsetAsync(p, 0, sizeof *p, s) != hipSuccess) return nullptr;
-    *slot = k;
-    return p;
+    if (std::getenv("OVS_NO_DYN")) return {};             // A/B: static slices only
+    if (n < (1ull << 18)) return {};                      // small batches: static slices (no memset, no event)
+    return c->dyn.acquire(s);
 }
 
-static void dyn_release(ovs_ctx* c, hipStream_t s, int slot)
+// a CallFrame's or a cached buffer's failure as the call's status
+ovs_status device_fail(ovs_ctx* c, hipError_t e, const std::string& what)
 {
-    if (slot < 0) return;
-    if (hipEventRecord(c->dyn_ev[slot], s) == hipSuccess) c->dyn_used[slot] = true;
-    else hipStreamSynchronize(s);                          // no event: the slot is free once the stream is
+    return fail(c, e == hipErrorOutOfMemory ? OVS_ENOMEM : OVS_EDEVICE, what + ": " + hipGetErrorString(e));
 }
 
-ovs_status kvis_acquire(ovs_ctx* c, uint64_t need, hipStream_t s, uint32_t** out)
-{
-    if (!c->kvis_ev) {
-        const hipError_t e = hipEventCreateWithFlags(&c->kvis_ev, hipEventDisableTiming);
-        if (e != hipSuccess) { c->kvis_ev = nullptr; return fail(c, OVS_EDEVICE, std::string("kvis event: ") + hipGetErrorString(e)); }
-    }
-    if (c->kvis_cap < need) {
-        if (c->kvis) {
-            if (c->kvis_used) {
-                const hipError_t e = hipEventSynchronize(c->kvis_ev);
-                if (e != hipSuccess) return fail(c, OVS_EDEVICE, std::string("kvis wait: ") + hipGetErrorString(e));
-            }
-            hipFree(c->kvis);
-            c->kvis = nullptr; c->kvis_cap = 0; c->kvis_used = false;
-        }
-        const hipError_t e = hipMalloc(&c->kvis, sizeof(uint32_t) * need);
-        if (e != hipSuccess) { c->kvis = nullptr; return fail(c, OVS_ENOMEM, "kvis allocation"); }
-        c->kvis_cap = need;
-    } else if (c->kvis_used) {
-        const hipError_t e = hipStreamWaitEvent(s, c->kvis_ev, 0);
-        if (e != hipSuccess) return fail(c, OVS_EDEVICE, std::string("kvis stream wait: ") + hipGetErrorString(e));
-    }
-    *out = c->kvis;
-    return OVS_OK;
-}
+ovs_status frame_fail(ovs_ctx* c, const CallFrame& F) { return device_fail(c, F.error(), F.what()); }
 
-void kvis_release(ovs_ctx* c, hipStream_t s)
+ovs_status lease_fail(ovs_ctx* c, const char* name, const CachedBuf::Lease& L)
 {
-    if (c->kvis_ev && hipEventRecord(c->kvis_ev, s) == hipSuccess) c->kvis_used = true;
+    return device_fail(c, L.error(), std::string(name) + " " + L.what());
 }
 
 // K1 key order, opt-in (OVS_K1_SORT=1): one-way iterative Chord batches of at least
@@ -270,54 +215,6 @@ bool ksort_wanted(uint64_t n)
     const char* m = std::getenv("OVS_K1_SORT_MIN");
     const uint64_t lim = m ? (uint64_t)std::strtoull(m, nullptr, 10) : (1ull << 20);
     return on != 0 && n >= lim && n < 0xFFFFFFFFull;
-}
-
-// the key-order buffers for n lookups: sorted keys, sources, caller indices, the sort's scratch
-ovs_status ks_acquire(ovs_ctx* c, uint64_t n, hipStream_t s, K160** skeys, uint32_t** ssrc, uint32_t** perm,
-                      uint32_t** scr)
-{
-    const uint64_t need = n * (sizeof(K160) + 8) + 4 * ksort_scratch_words() + 256;
-    if (!c->ks_ev) {
-        const hipError_t e = hipEventCreateWithFlags(&c->ks_ev, hipEventDisableTiming);
-        if (e != hipSuccess) { c->ks_ev = nullptr; return fail(c, OVS_EDEVICE, std::string("ks event: ") + hipGetErrorString(e)); }
-    }
-    if (c->ks_cap < need) {
-        if (c->ks) {
-            if (c->ks_used) {
-                const hipError_t e = hipEventSynchronize(c->ks_ev);
-                if (e != hipSuccess) return fail(c, OVS_EDEVICE, std::string("ks wait: ") + hipGetErrorString(e));
-            }
-            hipFree(c->ks);
-            c->ks = nullptr; c->ks_cap = 0; c->ks_used = false;
-        }
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->ks), need);
-        if (e != hipSuccess) { c->ks = nullptr; return fail(c, OVS_ENOMEM, "key-order buffers"); }
-        c->ks_cap = need;
-    } else if (c->ks_used) {
-        const hipError_t e = hipStreamWaitEvent(s, c->ks_ev, 0);
-        if (e != hipSuccess) return fail(c, OVS_EDEVICE, std::string("ks stream wait: ") + hipGetErrorString(e));
-    }
-    uint8_t* p = c->ks;
-    *scr = reinterpret_cast<uint32_t*>(p);
-    p += 4 * ksort_scratch_words();
-    *perm = reinterpret_cast<uint32_t*>(p);
-    p += 4 * n;
-    *ssrc = reinterpret_cast<uint32_t*>(p);
-    p += 4 * n;
-    *skeys = reinterpret_cast<K160*>(p);
-    return OVS_OK;
-}
-
-void ks_release(ovs_ctx* c, hipStream_t s)
-{
-    if (c->ks_ev && hipEventRecord(c->ks_ev, s) == hipSuccess) c->ks_used = true;
-}
-
-void free_scratch(ovs_ctx* c)
-{
-    for (void* p : c->scratch)
-        if (p) hipFree(p);
-    c->scratch.clear();
 }
 
 // SimTime(double) on the host (identical IEEE double arithmetic to the device path)
@@ -426,14 +323,14 @@ ovs_status check_extended_fingers(ovs_ctx* c, const ovs_params& P)
     if (P.routingType != 0) return OVS_OK;     // recursive routes: route messages, no RPC timeouts
     if (!c->bbox_ok) {
         if (!c->xy || c->n == 0) return fail(c, OVS_ESTATE, "no network loaded");
-        double* d = nullptr;
-        HIPCHK(c, hipMalloc(&d, sizeof(double) * 4 * 256));
+        CallFrame F(false, c->stream);
+        double* d = F.scratch<double>(4 * 256);
+        if (!F.ok()) return frame_fail(c, F);
         int blocks = 0;
         double h[4 * 256];
         hipError_t e = launch_xy_bbox(c->xy, c->n, d, &blocks, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(double) * 4 * blocks, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        hipFree(d);
         if (e != hipSuccess) return hip_fail(c, e, "coordinate bounding box");
         c->bbox[0] = h[0]; c->bbox[1] = h[1]; c->bbox[2] = h[2]; c->bbox[3] = h[3];
         for (int b = 1; b < blocks; ++b) {
@@ -473,32 +370,6 @@ ovs_status check_chord_route(ovs_ctx* c, const ovs_params& P)
                     "Chord route kernel implements lookupRedundantNodes=1, lookupParallelRpcs=1, numSiblings=1");
     return OVS_OK;
 }
-
-template <class T>
-ovs_status to_device(ovs_ctx* c, const T* src, uint64_t count, bool dev, T** out, bool* owned)
-{
-    if (dev) { *out = const_cast<T*>(src); *owned = false; return OVS_OK; }
-    T* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(T) * (count ? count : 1)));
-    if (count) HIPCHK(c, hipMemcpyAsync(d, src, sizeof(T) * count, hipMemcpyHostToDevice, c->stream));
-    *out = d; *owned = true;
-    return OVS_OK;
-}
-
-// device buffers of one call, freed on every path (early returns included)
-struct DevBufs {
-    std::vector<void*> p;
-    template <class T>
-    hipError_t get(T** out, uint64_t count)
-    {
-        *out = nullptr;
-        const hipError_t e = hipMalloc(out, sizeof(T) * (count ? count : 1));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    void own(void* q, bool owned) { if (owned && q) p.push_back(q); }
-    ~DevBufs() { for (void* q : p) hipFree(q); }
-};
 
 ChordView chord_view(const ovs_ctx* c)
 {
@@ -551,14 +422,13 @@ ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const dou
                                dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->xy, xy, sizeof(double2) * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                              c->stream));
-    uint32_t* bad = nullptr;
-    HIPCHK(c, hipMalloc(&bad, sizeof(uint32_t)));
+    CallFrame F(false, c->stream);
+    uint32_t hbad = 0;
+    uint32_t* bad = F.out(&hbad, 1);
+    if (!F.ok()) return frame_fail(c, F);
     HIPCHK(c, hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
     HIPCHK(c, launch_check_sorted(c->recs, (uint32_t)n, bad, c->stream));
-    uint32_t hbad = 0;
-    HIPCHK(c, hipMemcpyAsync(&hbad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(bad);
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     if (hbad) return fail(c, OVS_EINVAL, "node ids must be sorted ascending and unique");
     c->n = n;
     return OVS_OK;
@@ -603,14 +473,11 @@ void ovs_ctx_destroy(ovs_ctx* c)
     if (c->stream) hipStreamSynchronize(c->stream);
     free_tables(c);
     free_kad_shard(c);
-    free_scratch(c);
     kad_exhaustive_release(c->device);
     if (c->d_bounds) hipFree(c->d_bounds);
-    if (c->kvis_ev) hipEventDestroy(c->kvis_ev);
-    if (c->ks_ev) hipEventDestroy(c->ks_ev);
-    for (int i = 0; i < ovs_ctx::DYN_SLOTS; ++i)
-        if (c->dyn_ev[i]) hipEventDestroy(c->dyn_ev[i]);
-    if (c->dyn) hipFree(c->dyn);
+    c->kvis.destroy();
+    c->ks.destroy();
+    c->dyn.destroy();
     if (c->route_scratch && c->route_scratch_release) c->route_scratch_release(c->route_scratch);
     for (auto& kv : c->stage) stage_free(kv.second);
     for (hipStream_t cs : c->cohort)
@@ -769,13 +636,10 @@ static ovs_status shard_step(ovs_ctx* c, int ns, const ovs_lookup_rec* in, uint6
     }
     st = ensure_nodes(c, s);
     if (st != OVS_OK) return st;
-    int slot = -1;
-    unsigned long long* dyn = dyn_acquire(c, n_in, s, &slot);
-    const hipError_t e = launch_chord_shard_step(chord_view(c), DC, LC, c->d_bounds, (int)nshards, me, in, n_in, out,
-                                                 out_cap, out_count, done, done_cap, done_count, c->stage[s], c->num_cu,
-                                                 s, reinterpret_cast<const K160*>(fkeys), fsrc, fqid, dyn);
-    dyn_release(c, s, slot);
-    HIPCHK(c, e);
+    const DynSlots::Lease dyn = dyn_acquire(c, n_in, s);
+    HIPCHK(c, launch_chord_shard_step(chord_view(c), DC, LC, c->d_bounds, (int)nshards, me, in, n_in, out, out_cap,
+                                      out_count, done, done_cap, done_count, c->stage[s], c->num_cu, s,
+                                      reinterpret_cast<const K160*>(fkeys), fsrc, fqid, dyn.get()));
     return OVS_OK;
 }
 
@@ -876,12 +740,11 @@ ovs_status ovs_chord_export_fingers(ovs_ctx* c, uint32_t* out)
         HIPCHK(c, hipMemcpy(out, c->fres, sizeof(uint32_t) * tot, hipMemcpyDeviceToHost));
         return OVS_OK;
     }
-    uint32_t* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, sizeof(uint32_t) * tot));
+    CallFrame F(false, c->stream);
+    uint32_t* d = F.out(out, tot);
+    if (!F.ok()) return frame_fail(c, F);
     HIPCHK(c, launch_chord_export(c->recs, c->fingers, (uint32_t)c->n, d, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(uint32_t) * tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(d);
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -1030,12 +893,12 @@ ovs_status ovs_kad_load_tables(ovs_ctx* c, const ovs_key160* ids, uint64_t n, co
     ovs_status s = upload_nodes(c, ids, n, xy, false);
     if (s != OVS_OK) { free_tables(c); return s; }
     const uint64_t S5 = 5ull * (uint64_t)c->P.s, k = (uint64_t)c->P.k;
-    uint32_t *dsib = nullptr, *dbn = nullptr;
-    uint8_t* dbc = nullptr;
-    auto release = [&]() { if (dsib) hipFree(dsib); if (dbn) hipFree(dbn); if (dbc) hipFree(dbc); };
-    if (hipMalloc(&dsib, sizeof(uint32_t) * n * S5) != hipSuccess || hipMalloc(&dbc, n * 160) != hipSuccess ||
-        hipMalloc(&dbn, sizeof(uint32_t) * n * 160 * k) != hipSuccess) {
-        release(); free_tables(c);
+    CallFrame F(false, c->stream);
+    uint32_t* dsib = F.scratch<uint32_t>(n * S5);
+    uint8_t* dbc = F.scratch<uint8_t>(n * 160);
+    uint32_t* dbn = F.scratch<uint32_t>(n * 160 * k);
+    if (!F.ok()) {
+        free_tables(c);
         return fail(c, OVS_ENOMEM, "explicit Kademlia tables: device allocation failed");
     }
     hipError_t e = hipMemcpy(dsib, siblings, sizeof(uint32_t) * n * S5, hipMemcpyHostToDevice);
@@ -1045,7 +908,6 @@ ovs_status ovs_kad_load_tables(ovs_ctx* c, const ovs_key160* ids, uint64_t n, co
     if (e == hipSuccess)
         e = kad_build_explicit(c->recs, c->xy, (uint32_t)n, c->P.k, c->P.s, dsib, dbc, dbn, c->kad, &bad_node, &bad_code,
                                c->stream);
-    release();
     if (e == hipErrorInvalidValue && bad_code) {
         static const char* why[] = {"", "sibling index out of range or the node itself", "sibling listed twice",
                                     "bucket holds more than k entries", "bucket member out of range or the node itself",
@@ -1120,9 +982,11 @@ ovs_status ovs_kad_load_tables_csr(ovs_ctx* c, const ovs_key160* ids, uint64_t n
     for (uint64_t j = 0; j <= dir; ++j) off32[j] = (uint32_t)bucket_off[j];
     std::vector<int> caps(nb);
     for (int m = 0; m < nb; ++m) caps[m] = kad_bucket_size_host(P, m);
-    DevBufs d;
-    uint32_t *dsib = nullptr, *doff = nullptr, *dmem = nullptr;
-    if (d.get(&dsib, n * S5) != hipSuccess || d.get(&doff, dir + 1) != hipSuccess || d.get(&dmem, total) != hipSuccess) {
+    CallFrame F(false, c->stream);
+    uint32_t* dsib = F.scratch<uint32_t>(n * S5);
+    uint32_t* doff = F.scratch<uint32_t>(dir + 1);
+    uint32_t* dmem = F.scratch<uint32_t>(total);
+    if (!F.ok()) {
         free_tables(c);
         return fail(c, OVS_ENOMEM, "CSR Kademlia tables: device allocation failed");
     }
@@ -1414,12 +1278,11 @@ ovs_status ovs::kad_mig_step_impl(ovs_ctx* c, const void* in, uint64_t n_in, con
         HIPCHK(c, hipMemsetAsync(c->kbad, 0, sizeof(unsigned long long), s));
     }
     if (reset_errors) HIPCHK(c, hipMemsetAsync(c->kbad, 0, sizeof(unsigned long long), s));
-    int slot = -1;
-    unsigned long long* dyn = dyn_acquire(c, n_in, s, &slot);
+    const DynSlots::Lease dyn = dyn_acquire(c, n_in, s);
     hipError_t e = kad_mig_step(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), in, n_in,
                                 reinterpret_cast<const K160*>(fkeys), fsrc, fqid, c->d_bounds, (int)nshards, me, out,
-                                out_cap, out_count, done, done_cap, done_count, c->kbad, c->num_cu, c->stage[s], s, dyn);
-    dyn_release(c, s, slot);
+                                out_cap, out_count, done, done_cap, done_count, c->kbad, c->num_cu, c->stage[s], s,
+                                dyn.get());
     if (e != hipSuccess) return hip_fail(c, e, "kademlia migration step");
     return OVS_OK;
 }
@@ -1494,23 +1357,15 @@ ovs_status ovs_koorde_find_node_batch(ovs_ctx* c, const uint32_t* node, const ov
     HIPCHK(c, hipSetDevice(c->device));
     for (uint64_t i = 0; i < n; ++i)
         if (node[i] >= c->n) return fail(c, OVS_EINVAL, "node index out of range");
-    uint32_t *dn = nullptr, *dnext = nullptr;
-    K160* dk = nullptr;
-    KExt* de = nullptr;
-    bool o1, o2;
-    ovs_status st = to_device(c, node, n, false, &dn, &o1);
-    if (st != OVS_OK) return st;
-    st = to_device(c, reinterpret_cast<const K160*>(keys), n, false, &dk, &o2);
-    if (st != OVS_OK) { hipFree(dn); return st; }
-    HIPCHK(c, hipMalloc(&de, sizeof(KExt) * n));
-    HIPCHK(c, hipMalloc(&dnext, sizeof(uint32_t) * n));
-    HIPCHK(c, hipMemcpyAsync(de, ext, sizeof(KExt) * n, hipMemcpyHostToDevice, c->stream));
+    CallFrame F(false, c->stream);
+    const uint32_t* dn = F.in(node, n);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    KExt* de = F.inout(reinterpret_cast<KExt*>(ext), n);
+    uint32_t* dnext = F.out(next, n);
+    if (!F.ok()) return frame_fail(c, F);
     hipError_t e = koorde_find_node(c->koorde, c->recs, dn, dk, de, dnext, n, c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "koorde findNode kernel");
-    HIPCHK(c, hipMemcpyAsync(ext, de, sizeof(KExt) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(next, dnext, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(dn); hipFree(dk); hipFree(de); hipFree(dnext);
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -1582,37 +1437,21 @@ ovs_status ovs_epichord_find_node_batch(ovs_ctx* c, const uint32_t* node, const 
             if (node[i] >= c->n || (src[i] != NONE && src[i] >= c->n))
                 return fail(c, OVS_EINVAL, "node / source index out of range");
     }
-    uint32_t *dn = nullptr, *dsrc = nullptr, *dout = nullptr;
-    K160* dk = nullptr;
-    int64_t *dnow = nullptr, *dlast = nullptr;
-    uint8_t *dc = nullptr, *dst = nullptr;
-    bool o1 = false, o2 = false, o3 = false, o4 = false;
-    DevBufs own;          // the temporaries of a host-buffer call, freed on every path
-    ovs_status st = to_device(c, node, n, dev, &dn, &o1);
-    own.own(dn, o1);
-    if (st == OVS_OK) { st = to_device(c, reinterpret_cast<const K160*>(keys), n, dev, &dk, &o2); own.own(dk, o2); }
-    if (st == OVS_OK) { st = to_device(c, src, n, dev, &dsrc, &o3); own.own(dsrc, o3); }
-    if (st == OVS_OK) { st = to_device(c, now_ns, n, dev, &dnow, &o4); own.own(dnow, o4); }
-    if (st != OVS_OK) return st;
-    if (!dev) {
-        HIPCHK(c, own.get(&dout, n * max_out));
-        HIPCHK(c, own.get(&dlast, n * max_out));
-        HIPCHK(c, own.get(&dc, n));
-        HIPCHK(c, own.get(&dst, n));
-    } else {
-        dout = out_nodes; dlast = out_last_ns; dc = out_count; dst = out_status;
-    }
+    CallFrame F(dev, s);
+    const uint32_t* dn = F.in(node, n);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* dsrc = F.in(src, n);
+    const int64_t* dnow = F.in(now_ns, n);
+    uint32_t* dout = F.out(out_nodes, n * max_out);
+    int64_t* dlast = F.out(out_last_ns, n * max_out);
+    uint8_t* dc = F.out(out_count, n);
+    uint8_t* dst = F.out(out_status, n);
+    if (!F.ok()) return frame_fail(c, F);
     const int64_t ttl = simtime_host(c->P.cacheTTL, c->P.simtimeRound);
     hipError_t e = epichord_find_node(c->epi, c->recs, dn, dk, dsrc, dnow, n, numRedundantNodes, ttl, dout, dlast,
                                       max_out, dc, dst, s);
     if (e != hipSuccess) return hip_fail(c, e, "EpiChord findNode kernel");
-    if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(out_nodes, dout, sizeof(uint32_t) * n * max_out, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(out_last_ns, dlast, sizeof(int64_t) * n * max_out, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(out_count, dc, n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(out_status, dst, n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -1667,21 +1506,11 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
     if (n == 0) return OVS_OK;
     st = check_sources(c, src, n, dev);
     if (st != OVS_OK) return st;
-    // stage inputs
-    K160* dk = nullptr; uint32_t* ds = nullptr; ovs_route_out* dout = nullptr;
-    uint32_t* dhop = nullptr; uint32_t* drpc = nullptr;
-    bool ok_k = false, ok_s = false;
-    if (!dev) {
-        st = to_device(c, reinterpret_cast<const K160*>(keys), n, false, &dk, &ok_k);
-        if (st != OVS_OK) return st;
-        st = to_device(c, src, n, false, &ds, &ok_s);
-        if (st != OVS_OK) { hipFree(dk); return st; }
-        HIPCHK(c, hipMalloc(&dout, sizeof(ovs_route_out) * n));
-    } else {
-        dk = const_cast<K160*>(reinterpret_cast<const K160*>(keys));
-        ds = const_cast<uint32_t*>(src);
-        dout = out;
-    }
+    CallFrame F(dev, s);
+    CachedBuf::Lease vis;
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dout = F.out(out, n);
     // hop sequence buffer: always needed for explicit Chord tables and Koorde (the visited check).
     // Koorde without a hop_seq request uses a context scratch buffer, unpadded: K3 reads back only
     // the entries a lookup wrote
@@ -1691,79 +1520,59 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
     // source-routing-recursive Kademlia: the hop list is the message's visitedHops
     const bool kad_src = c->overlay == OVS_OVERLAY_KADEMLIA && c->P.routingType == 4;
     const bool need_hop = hop_seq || (c->overlay == OVS_OVERLAY_CHORD && !c->ideal) || kad_exh || kad_src;
-    bool own_hop = false;
-    if (koorde_scratch) {
-        {
-            const ovs_status ks = kvis_acquire(c, n * (uint64_t)H, s, &dhop);
-            if (ks != OVS_OK) return ks;
-        }
-    } else if (need_hop) {
-        if (dev && hop_seq) {
-            dhop = hop_seq;
-        } else if (!hop_seq) {
-            // an internal hop list (explicit Chord tables, exhaustive Kademlia: the visited sets) in the
-            // context's cached buffer, not a per-call allocation
-            {
-                const ovs_status ks = kvis_acquire(c, n * (uint64_t)H, s, &dhop);
-                if (ks != OVS_OK) return ks;
-            }
-        } else {
-            HIPCHK(c, hipMalloc(&dhop, sizeof(uint32_t) * n * H));
-            own_hop = true;
-        }
-        HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+    uint32_t* dhop = nullptr;
+    if (hop_seq) {
+        dhop = F.out(hop_seq, n * (uint64_t)H);
+    } else if (koorde_scratch || need_hop) {
+        // an internal hop list (Koorde, explicit Chord tables, exhaustive Kademlia: the visited sets) in
+        // the context's cached buffer, not a per-call allocation
+        vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
+        if (!vis) return lease_fail(c, "kvis", vis);
+        dhop = reinterpret_cast<uint32_t*>(vis.data());
     }
-    bool own_rpc = false;
-    if (rpcs) {
-        if (dev) drpc = rpcs;
-        else { HIPCHK(c, hipMalloc(&drpc, sizeof(uint32_t) * n)); own_rpc = true; }
-    }
+    uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
+    if (dhop && !koorde_scratch) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
     hipError_t e;
     if (c->overlay == OVS_OVERLAY_CHORD) {
         LookupConsts LC{c->P.hopCountMax, c->P.numSiblings, c->P.lookupRedundantNodes, c->P.routingType != 0};
-        if (drpc) {
-            // Chord with alpha = 1: one FindNodeCall per hop; filled after the route below
-        }
         if (c->ideal && !LC.recursive && ksort_wanted(n)) {
-            // key order: the batch sorted by its keys' top bits, results written at the caller's indices
-            K160* sk = nullptr;
-            uint32_t *ss = nullptr, *pm = nullptr, *scr = nullptr;
-            const ovs_status ks = ks_acquire(c, n, s, &sk, &ss, &pm, &scr);
-            if (ks != OVS_OK) return ks;
+            // key order: the batch sorted by its keys' top bits, results written at the caller's indices, in
+            // the context's key-order buffers: the sort's scratch, caller indices, sorted sources and keys
+            const CachedBuf::Lease ks = c->ks.acquire(n * (sizeof(K160) + 8) + 4 * ksort_scratch_words() + 256, s);
+            if (!ks) return lease_fail(c, "key-order buffers", ks);
+            uint32_t* scr = reinterpret_cast<uint32_t*>(ks.data());
+            uint32_t* pm = scr + ksort_scratch_words();
+            uint32_t* ss = pm + n;
+            K160* sk = reinterpret_cast<K160*>(ss + n);
             const char* kb = std::getenv("OVS_K1_SORT_BITS");
             e = ksort_launch(dk, ds, n, scr, sk, ss, pm, kb ? std::atoi(kb) : 14, s);
             if (e == hipSuccess)
                 e = launch_chord_route(chord_view(c), c->ideal, delay_consts(c->P), LC, sk, ss, n, dout, dhop, c->num_cu,
                                        s, pm);
-            ks_release(c, s);
         } else {
-            int slot = -1;
-            unsigned long long* dyn = dyn_acquire(c, n, s, &slot);
+            const DynSlots::Lease dyn = dyn_acquire(c, n, s);
             e = launch_chord_route(chord_view(c), c->ideal, delay_consts(c->P), LC, dk, ds, n, dout, dhop, c->num_cu, s,
-                                   nullptr, dyn);
-            dyn_release(c, s, slot);
+                                   nullptr, dyn.get());
         }
         if (e == hipSuccess && drpc) {
             if (LC.recursive) e = hipMemsetAsync(drpc, 0, sizeof(uint32_t) * n, s);   // no FindNodeCalls
             else e = launch_fill_rpcs_from_hops(dout, n, drpc, s);
         }
     } else if (c->overlay == OVS_OVERLAY_KOORDE) {
-        int slot = -1;
-        unsigned long long* dyn = dyn_acquire(c, n, s, &slot);
+        const DynSlots::Lease dyn = dyn_acquire(c, n, s);
         e = koorde_route(c->koorde, c->recs, c->xy, delay_consts(c->P), c->P.hopCountMax, dk, ds, n, dout, dhop,
-                         !koorde_scratch, drpc, c->num_cu, s, dyn);
-        dyn_release(c, s, slot);
+                         !koorde_scratch, drpc, c->num_cu, s, dyn.get());
     } else if (kad_exh) {
         // sendToKey with EXHAUSTIVE_ITERATIVE_ROUTING (BaseOverlay.cc:1434-1442): lookup(key, numSiblings = 1)
         // with redundantNodes = lookupRedundantNodes, the route message to getResult()[0]
-        uint32_t* dres = nullptr;
-        HIPCHK(c, hipMalloc(&dres, sizeof(uint32_t) * n));
+        uint32_t* dres = F.scratch<uint32_t>(n);
+        if (!F.ok()) return frame_fail(c, F);
         bool cap_err = false;
         // dhop was filled with NONE above: the kernel leaves the rows unpadded
         e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), c->P.lookupRedundantNodes, 1, true,
                            dk, ds, n, dout, dres, dhop, nullptr, drpc, c->num_cu, s, &cap_err, nullptr, false,
                            hop_seq == nullptr /* nobody reads the visited sets: their first entries in LDS */);
-        hipFree(dres);
         if (e == hipSuccess && cap_err) return fail(c, OVS_ENOTSUP, "a lookup exceeded the kernel's capacity (64 timed-out nodes)");
     } else if (c->P.routingType == 1 || c->P.routingType == 2 || kad_src) {
         // R/Kademlia: recursive routing with Kademlia's recursiveRoutingHook (kad_general.hip)
@@ -1774,25 +1583,13 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
         e = kad_route_general(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), dk, ds, n, dout, dhop, drpc, s,
                               nullptr);
     } else {
-        int slot = -1;
-        unsigned long long* dyn = dyn_acquire(c, n, s, &slot);
+        const DynSlots::Lease dyn = dyn_acquire(c, n, s);
         e = kad_route(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), dk, ds, n, dout, dhop, drpc,
-                      c->num_cu, s, nullptr, dyn);
-        dyn_release(c, s, slot);
+                      c->num_cu, s, nullptr, dyn.get());
     }
-    if (dhop && dhop == c->kvis) kvis_release(c, s);
+    vis.release();
     if (e != hipSuccess) return hip_fail(c, e, "route kernel");
-    if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(ovs_route_out) * n, hipMemcpyDeviceToHost, s));
-        if (hop_seq) HIPCHK(c, hipMemcpyAsync(hop_seq, dhop, sizeof(uint32_t) * n * H, hipMemcpyDeviceToHost, s));
-        if (rpcs) HIPCHK(c, hipMemcpyAsync(rpcs, drpc, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        hipFree(dk); hipFree(ds); hipFree(dout);
-    } else if (own_hop || own_rpc) {
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    if (own_hop) hipFree(dhop);
-    if (own_rpc) hipFree(drpc);
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -1859,22 +1656,14 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
         DC.msgRespSib = 2 * simtime_host((double)((int64_t)(DC.respBase + DC.respPerNode * nodes) * 8) / P.datarate,
                                          P.simtimeRound) + DC.access2;
     }
-    K160* dk = nullptr; uint32_t* ds = nullptr; ovs_route_out* dout = nullptr; uint32_t* dsib = nullptr;
+    CallFrame F(dev, s);
+    CachedBuf::Lease vis;
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dout = F.out(reinterpret_cast<ovs_route_out*>(out), n);
+    uint32_t* dsib = F.out(siblings, n * (uint64_t)nslots);
+    if (!F.ok()) return frame_fail(c, F);
     uint32_t* dhop = nullptr;
-    bool ok_k = false, ok_s = false;
-    if (!dev) {
-        st = to_device(c, reinterpret_cast<const K160*>(keys), n, false, &dk, &ok_k);
-        if (st != OVS_OK) return st;
-        st = to_device(c, src, n, false, &ds, &ok_s);
-        if (st != OVS_OK) { hipFree(dk); return st; }
-        HIPCHK(c, hipMalloc(&dout, sizeof(ovs_route_out) * n));
-        HIPCHK(c, hipMalloc(&dsib, sizeof(uint32_t) * n * nslots));
-    } else {
-        dk = const_cast<K160*>(reinterpret_cast<const K160*>(keys));
-        ds = const_cast<uint32_t*>(src);
-        dout = reinterpret_cast<ovs_route_out*>(out);
-        dsib = siblings;
-    }
     // Chord exact-key lookups replay the one-way chain recorded one hop beyond hopCountMax
     const bool chord_exact = chord && ns == 0;
     const int H = chord_exact ? P.hopCountMax + 1 : P.hopCountMax > 0 ? P.hopCountMax : 1;
@@ -1882,10 +1671,9 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
     const bool need_hop = (chord && !c->ideal) || kad_exh || chord_exact || (kad_rec && P.routingType == 4);
     if (need_hop) {
         // internal (a LookupCall records no hop sequence): the context's cached buffer
-        {
-            const ovs_status ks = kvis_acquire(c, n * (uint64_t)H, s, &dhop);
-            if (ks != OVS_OK) return ks;
-        }
+        vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
+        if (!vis) return lease_fail(c, "kvis", vis);
+        dhop = reinterpret_cast<uint32_t*>(vis.data());
         HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
     }
     hipError_t e;
@@ -1899,10 +1687,8 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
             e = launch_chord_exact_finish(chord_view(c), delay_consts(P), P.hopCountMax, dk, ds, dhop, H, dout, n, s);
     } else if (chord) {
         LookupConsts LC{P.hopCountMax, ns, P.lookupRedundantNodes, 0};
-        int slot = -1;
-        unsigned long long* dyn = dyn_acquire(c, n, s, &slot);
-        e = launch_chord_route(chord_view(c), c->ideal, DC, LC, dk, ds, n, dout, dhop, c->num_cu, s, nullptr, dyn);
-        dyn_release(c, s, slot);
+        const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+        e = launch_chord_route(chord_view(c), c->ideal, DC, LC, dk, ds, n, dout, dhop, c->num_cu, s, nullptr, dyn.get());
     } else if (kad_exh) {
         // lookupRpc with EXHAUSTIVE_ITERATIVE_ROUTING: redundantNodes = lookupRedundantNodes, numSiblings = ns
         bool cap_err = false;
@@ -1920,26 +1706,14 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
     } else if (c->kad.general) {
         e = kad_route_general(c->kad, c->xy, (uint32_t)c->n, P, DC, dk, ds, n, dout, nullptr, nullptr, s, dsib);
     } else {
-        int slot = -1;
-        unsigned long long* dyn = dyn_acquire(c, n, s, &slot);
+        const DynSlots::Lease dyn = dyn_acquire(c, n, s);
         e = kad_route(c->kad, c->xy, (uint32_t)c->n, P, DC, dk, ds, n, dout, nullptr, nullptr, c->num_cu, s,
-                      dsib, dyn);
-        dyn_release(c, s, slot);
+                      dsib, dyn.get());
     }
     if (e == hipSuccess && !kad_exh) e = launch_lookup_finish(chord_view(c), chord, c->ideal, nslots, dout, dsib, n, s);
-    if (dhop && dhop == c->kvis) kvis_release(c, s);
-    if (e != hipSuccess) {
-        if (!dev) { hipFree(dk); hipFree(ds); hipFree(dout); hipFree(dsib); }
-        /* dhop: the context's cached buffer */
-        return hip_fail(c, e, "lookup kernel");
-    }
-    if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(ovs_lookup_out) * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(siblings, dsib, sizeof(uint32_t) * n * nslots, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        hipFree(dk); hipFree(ds); hipFree(dout); hipFree(dsib);
-    }
-    /* dhop: the context's cached buffer, ordered by kvis_ev: a device-pointer call stays asynchronous */
+    vis.release();      // dhop is ordered by the buffer's event: a device-pointer call stays asynchronous
+    if (e != hipSuccess) return hip_fail(c, e, "lookup kernel");
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -1964,65 +1738,36 @@ ovs_status ovs_kad_refresh_batch(ovs_ctx* c, const ovs_key160* keys, const uint3
     const bool dev = flags & OVS_DEVICE_PTRS;
     hipStream_t s = dev ? (hipStream_t)stream : c->stream;
     if (n == 0) return OVS_OK;
-    if (!dev)
-        for (uint64_t i = 0; i < n; ++i)
-            if (src[i] >= c->n) return fail(c, OVS_EINVAL, "source index out of range");
-    const uint64_t H = (uint64_t)P.hopCountMax;
-    K160* dk = nullptr; uint32_t* ds = nullptr; ovs_lookup_out* dout = nullptr; uint32_t* dsib = nullptr;
-    uint32_t* dresp = nullptr; int64_t* drtt = nullptr; uint32_t* drpc = nullptr;
-    bool ok_k = false, ok_s = false;
-    ovs_status st = to_device(c, reinterpret_cast<const K160*>(keys), n, dev, &dk, &ok_k);
+    const ovs_status st = check_sources(c, src, n, dev);
     if (st != OVS_OK) return st;
-    st = to_device(c, src, n, dev, &ds, &ok_s);
-    if (st != OVS_OK) { if (ok_k) hipFree(dk); return st; }
+    const uint64_t H = (uint64_t)P.hopCountMax;
+    CallFrame F(dev, s);
+    CachedBuf::Lease vis;
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_lookup_out* dout = F.out(out, n);
+    uint32_t* dsib = F.out(siblings, n * (uint64_t)R);
     // the responder list is the lookup's visited set: always present on the device -- when the
     // caller asked for none, in the context's cached buffer (as K3's; a per-call hipMalloc / hipFree
     // of n * hopCountMax entries had put an allocation and a device synchronisation into every call)
-    const bool internal_resp = !responders;
-    const bool own_resp = !dev && responders, own_rtt = !dev && rtt_ns, own_rpc = !dev && rpcs;
-    auto cleanup = [&]() {
-        if (ok_k) hipFree(dk);
-        if (ok_s) hipFree(ds);
-        if (!dev) { hipFree(dout); hipFree(dsib); }
-        if (own_resp) hipFree(dresp);
-        if (own_rtt) hipFree(drtt);
-        if (own_rpc) hipFree(drpc);
-    };
-    if (!dev) {
-        HIPCHK(c, hipMalloc(&dout, sizeof(ovs_lookup_out) * n));
-        HIPCHK(c, hipMalloc(&dsib, sizeof(uint32_t) * n * R));
-    } else { dout = out; dsib = siblings; }
-    if (internal_resp) {
-        {
-            const ovs_status ks = kvis_acquire(c, n * H, s, &dresp);
-            if (ks != OVS_OK) return ks;
-        }
-    } else if (own_resp) {
-        HIPCHK(c, hipMalloc(&dresp, sizeof(uint32_t) * n * H));
-    } else {
-        dresp = responders;
+    uint32_t* dresp = responders ? F.out(responders, n * H) : nullptr;
+    int64_t* drtt = rtt_ns ? F.out(rtt_ns, n * H) : nullptr;
+    uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
+    if (!responders) {
+        vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
+        if (!vis) return lease_fail(c, "kvis", vis);
+        dresp = reinterpret_cast<uint32_t*>(vis.data());
     }
-    if (own_rtt) HIPCHK(c, hipMalloc(&drtt, sizeof(int64_t) * n * H));
-    else drtt = rtt_ns;
-    if (own_rpc) HIPCHK(c, hipMalloc(&drpc, sizeof(uint32_t) * n));
-    else drpc = rpcs;
     bool cap_err = false;
     const hipError_t e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, P, delay_consts(P), R, R, false, dk, ds, n, dout,
                                         dsib, dresp, drtt, drpc, c->num_cu, s, &cap_err, nullptr,
                                         responders != nullptr /* else the internal visited lists: no padding */,
                                         responders == nullptr /* ... and their first entries in LDS */);
-    if (internal_resp) kvis_release(c, s);
-    if (e != hipSuccess) { cleanup(); return hip_fail(c, e, "refresh lookup kernel"); }
-    if (cap_err) { cleanup(); return fail(c, OVS_ENOTSUP, "a refresh lookup exceeded the kernel's capacity (64 timed-out nodes)"); }
-    if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(ovs_lookup_out) * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(siblings, dsib, sizeof(uint32_t) * n * R, hipMemcpyDeviceToHost, s));
-        if (responders) HIPCHK(c, hipMemcpyAsync(responders, dresp, sizeof(uint32_t) * n * H, hipMemcpyDeviceToHost, s));
-        if (rtt_ns) HIPCHK(c, hipMemcpyAsync(rtt_ns, drtt, sizeof(int64_t) * n * H, hipMemcpyDeviceToHost, s));
-        if (rpcs) HIPCHK(c, hipMemcpyAsync(rpcs, drpc, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    cleanup();
+    vis.release();
+    if (e != hipSuccess) return hip_fail(c, e, "refresh lookup kernel");
+    if (cap_err) return fail(c, OVS_ENOTSUP, "a refresh lookup exceeded the kernel's capacity (64 timed-out nodes)");
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -2039,14 +1784,11 @@ ovs_status kad_upload_host_tables(ovs_ctx* c)
         free_tables(c);    // the host copy was changed by the round: the device tables no longer match it
         return fail(c, OVS_ENOTSUP, "a bucket outgrew k (bucketType kademlia keeps k per bucket)");
     }
-    uint32_t *dsib = nullptr, *dbn = nullptr;
-    uint8_t* dbc = nullptr;
-    auto release = [&]() { if (dsib) hipFree(dsib); if (dbn) hipFree(dbn); if (dbc) hipFree(dbc); };
-    if (hipMalloc(&dsib, sizeof(uint32_t) * n * S5) != hipSuccess || hipMalloc(&dbc, n * 160) != hipSuccess ||
-        hipMalloc(&dbn, sizeof(uint32_t) * n * 160 * k) != hipSuccess) {
-        release();
-        return fail(c, OVS_ENOMEM, "maintenance round: device allocation failed");
-    }
+    CallFrame F(false, c->stream);
+    uint32_t* dsib = F.scratch<uint32_t>(n * S5);
+    uint8_t* dbc = F.scratch<uint8_t>(n * 160);
+    uint32_t* dbn = F.scratch<uint32_t>(n * 160 * k);
+    if (!F.ok()) return fail(c, OVS_ENOMEM, "maintenance round: device allocation failed");
     hipError_t e = hipMemcpy(dsib, hs.data(), sizeof(uint32_t) * n * S5, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dbc, hc.data(), n * 160, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dbn, hn.data(), sizeof(uint32_t) * n * 160 * k, hipMemcpyHostToDevice);
@@ -2061,7 +1803,6 @@ ovs_status kad_upload_host_tables(ovs_ctx* c)
     // test hook: OVS_FAULT_INJECT=kad_rebuild makes the rebuild report a broken invariant
     // (tests/test_gpu_kad_maint.py::test_failed_rebuild_leaves_no_tables)
     if (e == hipSuccess && fault_injected("kad_rebuild")) { e = hipErrorInvalidValue; bad_code = 99; }
-    release();
     if (e == hipSuccess) {
         kad_free(c->kad);
         c->kad = nt;
@@ -2140,28 +1881,27 @@ ovs_status ovs_kad_maintenance_round(ovs_ctx* c, const uint32_t* nodes, uint64_t
         std::vector<K160> gk(ng);
         std::vector<uint32_t> gs(ng);
         for (uint64_t q = 0; q < ng; ++q) { gk[q] = keys[ix[q]]; gs[q] = src[ix[q]]; }
-        DevBufs d;
-        K160* dk; uint32_t *ds, *dsib, *dresp, *drpc, *dcn; ovs_lookup_out* dout; int64_t *dta, *dct;
-        HIPCHK(c, d.get(&dk, ng)); HIPCHK(c, d.get(&ds, ng)); HIPCHK(c, d.get(&dsib, ng * (uint64_t)Rg));
-        HIPCHK(c, d.get(&dresp, ng * H)); HIPCHK(c, d.get(&drpc, ng)); HIPCHK(c, d.get(&dout, ng));
-        HIPCHK(c, d.get(&dta, ng * H)); HIPCHK(c, d.get(&dcn, ng * (uint64_t)ccap)); HIPCHK(c, d.get(&dct, ng * (uint64_t)ccap));
-        HIPCHK(c, hipMemcpyAsync(dk, gk.data(), sizeof(K160) * ng, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(ds, gs.data(), sizeof(uint32_t) * ng, hipMemcpyHostToDevice, s));
+        std::vector<uint32_t> hr(ng * H), hc(ng * (uint64_t)ccap);
+        std::vector<int64_t> hta(ng * H), hct(ng * (uint64_t)ccap);
+        std::vector<ovs_lookup_out> ho(ng);
+        CallFrame F(false, s);
+        const K160* dk = F.in(gk.data(), ng);
+        const uint32_t* ds = F.in(gs.data(), ng);
+        uint32_t* dsib = F.scratch<uint32_t>(ng * (uint64_t)Rg);
+        uint32_t* drpc = F.scratch<uint32_t>(ng);
+        uint32_t* dresp = F.out(hr.data(), ng * H);
+        int64_t* dta = F.out(hta.data(), ng * H);
+        uint32_t* dcn = F.out(hc.data(), ng * (uint64_t)ccap);
+        int64_t* dct = F.out(hct.data(), ng * (uint64_t)ccap);
+        ovs_lookup_out* dout = F.out(ho.data(), ng);
+        if (!F.ok()) return frame_fail(c, F);
         const KadExhTrace tr{dta, dcn, dct, ccap};
         bool cap_err = false;
         const hipError_t e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, P, DC, Rg, Rg, false, dk, ds, ng, dout, dsib,
                                             dresp, nullptr, drpc, c->num_cu, s, &cap_err, &tr);
         if (e != hipSuccess) return hip_fail(c, e, "maintenance round: refresh lookups");
         if (cap_err) return fail(c, OVS_ENOTSUP, "a refresh lookup exceeded the kernel's capacity");
-        std::vector<uint32_t> hr(ng * H), hc(ng * (uint64_t)ccap);
-        std::vector<int64_t> hta(ng * H), hct(ng * (uint64_t)ccap);
-        std::vector<ovs_lookup_out> ho(ng);
-        HIPCHK(c, hipMemcpyAsync(hr.data(), dresp, sizeof(uint32_t) * ng * H, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(hta.data(), dta, sizeof(int64_t) * ng * H, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(hc.data(), dcn, sizeof(uint32_t) * ng * ccap, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(hct.data(), dct, sizeof(int64_t) * ng * ccap, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(ho.data(), dout, sizeof(ovs_lookup_out) * ng, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
+        if (F.finish() != hipSuccess) return frame_fail(c, F);
         for (uint64_t q = 0; q < ng; ++q) {
             const uint64_t t = ix[q];
             std::copy(hr.begin() + q * H, hr.begin() + (q + 1) * H, resp.begin() + t * H);
@@ -2199,20 +1939,19 @@ ovs_status ovs_kad_maintenance_round(ovs_ctx* c, const uint32_t* nodes, uint64_t
                     for (int i = 0; i < nresp[t]; ++i) { pn.push_back(resp[t * H + i]); pk.push_back(keys[t]); pri.push_back(t * H + i); }
             const uint64_t np = pn.size();
             if (np == 0) continue;
-            DevBufs d;
-            uint32_t *dn, *dout; K160* dk; uint8_t *dcount, *dsb;
-            HIPCHK(c, d.get(&dn, np)); HIPCHK(c, d.get(&dk, np)); HIPCHK(c, d.get(&dout, np * (uint64_t)Rg));
-            HIPCHK(c, d.get(&dcount, np)); HIPCHK(c, d.get(&dsb, np));
-            HIPCHK(c, hipMemcpyAsync(dn, pn.data(), sizeof(uint32_t) * np, hipMemcpyHostToDevice, s));
-            HIPCHK(c, hipMemcpyAsync(dk, pk.data(), sizeof(K160) * np, hipMemcpyHostToDevice, s));
+            std::vector<uint32_t> ho(np * (uint64_t)Rg);
+            std::vector<uint8_t> hcount(np);
+            CallFrame F(false, s);
+            const uint32_t* dn = F.in(pn.data(), np);
+            const K160* dk = F.in(pk.data(), np);
+            uint32_t* dout = F.out(ho.data(), np * (uint64_t)Rg);
+            uint8_t* dcount = F.out(hcount.data(), np);
+            uint8_t* dsb = F.scratch<uint8_t>(np);
+            if (!F.ok()) return frame_fail(c, F);
             const hipError_t e = kad_find_node(c->kad, (uint32_t)c->n, P, dn, dk, np, Rg, -1, dout, (uint32_t)Rg, dcount,
                                                dsb, s);
             if (e != hipSuccess) return hip_fail(c, e, "maintenance round: findNode of the responses");
-            std::vector<uint32_t> ho(np * (uint64_t)Rg);
-            std::vector<uint8_t> hcount(np);
-            HIPCHK(c, hipMemcpyAsync(ho.data(), dout, sizeof(uint32_t) * np * Rg, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(hcount.data(), dcount, np, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
+            if (F.finish() != hipSuccess) return frame_fail(c, F);
             for (uint64_t q = 0; q < np; ++q) {
                 ncarried[pri[q]] = hcount[q];
                 std::copy(ho.begin() + q * Rg, ho.begin() + q * Rg + hcount[q], carried.begin() + roff[pri[q]]);
@@ -2257,33 +1996,18 @@ ovs_status ovs_kad_refresh_keys(ovs_ctx* c, const uint32_t* nodes, uint64_t m, c
     if (!dev)
         for (uint64_t i = 0; i < m; ++i)
             if (nodes[i] >= c->n) return fail(c, OVS_EINVAL, "node index out of range");
-    uint32_t* dn = nullptr; uint32_t* dst = nullptr; K160* dk = nullptr; uint32_t* dsrc = nullptr;
-    bool o1 = false, o2 = false;
-    ovs_status st = to_device(c, nodes, m, dev, &dn, &o1);
-    if (st != OVS_OK) return st;
-    if (stale) {
-        st = to_device(c, stale, m * 5, dev, &dst, &o2);
-        if (st != OVS_OK) { if (o1) hipFree(dn); return st; }
-    }
-    if (cap && !dev) {
-        HIPCHK(c, hipMalloc(&dk, sizeof(K160) * cap));
-        HIPCHK(c, hipMalloc(&dsrc, sizeof(uint32_t) * cap));
-    } else if (cap) {
-        dk = reinterpret_cast<K160*>(keys);
-        dsrc = src;
-    }
+    CallFrame F(dev, s);
+    const uint32_t* dn = F.in(nodes, m);
+    const uint32_t* dst = stale ? F.in(stale, m * 5) : nullptr;
+    K160* dk = cap ? F.out(reinterpret_cast<K160*>(keys), cap) : nullptr;
+    uint32_t* dsrc = cap ? F.out(src, cap) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
     uint64_t total = 0;
     const hipError_t e = kad_refresh_keys(c->kad, (uint32_t)c->n, dn, m, dst, dk, dsrc, cap, &total, s);
-    if (e == hipSuccess && cap && !dev) {
-        const uint64_t w = total < cap ? total : cap;
-        HIPCHK(c, hipMemcpyAsync(keys, dk, sizeof(K160) * w, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(src, dsrc, sizeof(uint32_t) * w, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    if (o1) hipFree(dn);
-    if (o2) hipFree(dst);
-    if (cap && !dev) { hipFree(dk); hipFree(dsrc); }
     if (e != hipSuccess) return hip_fail(c, e, "bucket refresh keys");
+    F.limit(dk, total);         // the kernel wrote min(total, cap) pairs
+    F.limit(dsrc, total);
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     *count = total;
     return OVS_OK;
 }
@@ -2311,22 +2035,18 @@ ovs_status ovs_find_node_batch(ovs_ctx* c, const uint32_t* node, const ovs_key16
     const bool dev = flags & OVS_DEVICE_PTRS;
     hipStream_t s = dev ? (hipStream_t)stream : c->stream;   // NULL = the default stream
     if (n == 0) return OVS_OK;
-    uint32_t* dn = nullptr; K160* dk = nullptr; uint32_t* dout = nullptr; uint8_t* dc = nullptr; uint8_t* dsb = nullptr;
-    bool o1, o2;
-    ovs_status st = to_device(c, node, n, dev, &dn, &o1);
-    if (st != OVS_OK) return st;
-    st = to_device(c, reinterpret_cast<const K160*>(keys), n, dev, &dk, &o2);
-    if (st != OVS_OK) return st;
-    if (!dev) {
-        HIPCHK(c, hipMalloc(&dout, sizeof(uint32_t) * n * max_out));
-        HIPCHK(c, hipMalloc(&dc, n));
-        HIPCHK(c, hipMalloc(&dsb, n));
-    } else { dout = out_nodes; dc = out_count; dsb = out_sibling; }
     // validate node indices on the host for host calls
     if (!dev) {
         for (uint64_t i = 0; i < n; ++i)
             if (node[i] >= c->n) return fail(c, OVS_EINVAL, "node index out of range");
     }
+    CallFrame F(dev, s);
+    const uint32_t* dn = F.in(node, n);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    uint32_t* dout = F.out(out_nodes, n * (uint64_t)max_out);
+    uint8_t* dc = F.out(out_count, n);
+    uint8_t* dsb = F.out(out_sibling, n);
+    if (!F.ok()) return frame_fail(c, F);
     hipError_t e;
     if (c->overlay == OVS_OVERLAY_CHORD)
         e = launch_chord_find_node(chord_view(c), c->ideal, dn, dk, n, numRedundantNodes, numSiblings, dout, max_out,
@@ -2338,13 +2058,7 @@ ovs_status ovs_find_node_batch(ovs_ctx* c, const uint32_t* node, const ovs_key16
         e = kad_find_node(c->kad, (uint32_t)c->n, c->P, dn, dk, n, numRedundantNodes, numSiblings, dout,
                           max_out, dc, dsb, s);
     if (e != hipSuccess) return hip_fail(c, e, "findNode kernel");
-    if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(out_nodes, dout, sizeof(uint32_t) * n * max_out, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(out_count, dc, n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(out_sibling, dsb, n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        hipFree(dn); hipFree(dk); hipFree(dout); hipFree(dc); hipFree(dsb);
-    }
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
@@ -2361,22 +2075,66 @@ ovs_status ovs_delay_batch(ovs_ctx* c, const uint32_t* a, const uint32_t* b, con
         for (uint64_t i = 0; i < n; ++i)
             if (a[i] >= c->n || b[i] >= c->n) return fail(c, OVS_EINVAL, "node index out of range");
     }
-    uint32_t *da, *db; int32_t* dbytes; int64_t* dout;
-    bool o1, o2, o3;
-    ovs_status st = to_device(c, a, n, dev, &da, &o1);
-    if (st == OVS_OK) st = to_device(c, b, n, dev, &db, &o2);
-    if (st == OVS_OK) st = to_device(c, bytes, n, dev, &dbytes, &o3);
-    if (st != OVS_OK) return st;
-    if (!dev) HIPCHK(c, hipMalloc(&dout, sizeof(int64_t) * n)); else dout = out_ns;
+    CallFrame F(dev, s);
+    const uint32_t* da = F.in(a, n);
+    const uint32_t* db = F.in(b, n);
+    const int32_t* dbytes = F.in(bytes, n);
+    int64_t* dout = F.out(out_ns, n);
+    if (!F.ok()) return frame_fail(c, F);
     hipError_t e = launch_delay(c->xy, delay_consts(c->P), da, db, dbytes, n, dout, s);
     if (e != hipSuccess) return hip_fail(c, e, "delay kernel");
-    if (!dev) {
-        HIPCHK(c, hipMemcpyAsync(out_ns, dout, sizeof(int64_t) * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        hipFree(da); hipFree(db); hipFree(dbytes); hipFree(dout);
-    }
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
+
+extern "C++" {
+namespace {
+
+// The statistics kernels over one staged batch: the scratch they reduce in, the launch, and the sums
+// (h) and per-node reductions (r, NSTAT rows of sum, sum of squares, min, max, count) read back.
+// The read-back synchronises the stream in both pointer modes: the results are host values.
+ovs_status run_stats(ovs_ctx* c, CallFrame& F, hipStream_t s, const ovs_route_out* dout, const K160* dk, const uint32_t* ds,
+                     uint64_t n, int32_t lookup_node_ids, double measured_time_s, uint64_t msg_bytes, const uint32_t* dsib,
+                     uint64_t sib_stride, StatsDev* h, double* r)
+{
+    StatsDev* S = F.scratch<StatsDev>(1);
+    uint32_t* counts = F.scratch<uint32_t>(3 * c->n);
+    double* partial = F.scratch<double>(STATS_NODE_BLOCKS * NSTAT * 5);
+    double* result = F.scratch<double>(NSTAT * 5);
+    if (!F.ok()) return frame_fail(c, F);
+    // GlobalStatistics::MIN_MEASURED = 0.1 s (GlobalStatistics.cc:32, KBRTestApp.cc:502)
+    const int rates = measured_time_s >= 0.1;
+    hipError_t e = launch_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids, measured_time_s, msg_bytes,
+                                rates, S, counts, partial, result, c->num_cu, s, dsib, sib_stride);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, S, sizeof *h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(r, result, sizeof(double) * NSTAT * 5, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(c, e, "statistics kernels");
+    return OVS_OK;
+}
+
+// cStdDev::getMean / getVariance (OMNeT++ 4.x) of row k of run_stats' reductions: sample variance, 0
+// below two values or if negative
+void finish_stddev(const double* r, int k, ovs_stddev& d)
+{
+    const double sum = r[k * 5 + 0], sq = r[k * 5 + 1];
+    uint64_t cnt;
+    std::memcpy(&cnt, &r[k * 5 + 4], sizeof cnt);
+    d.count = cnt;
+    if (!cnt) return;
+    d.mean = sum / (double)cnt;
+    double var = 0.0;
+    if (cnt > 1) {
+        var = (sq - sum * sum / (double)cnt) / (double)(cnt - 1);
+        if (var < 0) var = 0;
+    }
+    d.stddev = std::sqrt(var);
+    d.min = r[k * 5 + 2];
+    d.max = r[k * 5 + 3];
+}
+
+}  // namespace
+}  // extern "C++"
 
 ovs_status ovs_kbrtest_stats_batch(ovs_ctx* c, const ovs_route_out* out, const ovs_key160* keys, const uint32_t* src,
                                    uint64_t n, double measured_time_s, int32_t lookup_node_ids,
@@ -2388,48 +2146,15 @@ ovs_status ovs_kbrtest_stats_batch(ovs_ctx* c, const ovs_route_out* out, const o
     HIPCHK(c, hipSetDevice(c->device));
     const bool dev = flags & OVS_DEVICE_PTRS;
     hipStream_t s = dev ? (hipStream_t)stream : c->stream;   // NULL = the default stream
-    const ovs_route_out* dout = out;
-    const K160* dk = reinterpret_cast<const K160*>(keys);
-    const uint32_t* ds = src;
-    std::vector<void*> owned;
-    auto cleanup = [&]() { for (void* p : owned) hipFree(p); };
-    if (!dev && n) {
-        ovs_route_out* o; K160* k = nullptr; uint32_t* r; bool ow;
-        ovs_status st = to_device(c, out, n, false, &o, &ow);
-        if (st != OVS_OK) return st;
-        owned.push_back(o);
-        st = to_device(c, src, n, false, &r, &ow);
-        if (st != OVS_OK) { cleanup(); return st; }
-        owned.push_back(r);
-        if (lookup_node_ids) {
-            st = to_device(c, reinterpret_cast<const K160*>(keys), n, false, &k, &ow);
-            if (st != OVS_OK) { cleanup(); return st; }
-            owned.push_back(k);
-        }
-        dout = o; dk = k; ds = r;
-    }
-    StatsDev* S = nullptr; uint32_t* counts = nullptr; double* partial = nullptr; double* result = nullptr;
-    if (hipMalloc(&S, sizeof(StatsDev)) != hipSuccess ||
-        hipMalloc(&counts, sizeof(uint32_t) * 3 * c->n) != hipSuccess ||
-        hipMalloc(&partial, sizeof(double) * STATS_NODE_BLOCKS * NSTAT * 5) != hipSuccess ||
-        hipMalloc(&result, sizeof(double) * NSTAT * 5) != hipSuccess) {
-        owned.push_back(S); owned.push_back(counts); owned.push_back(partial); owned.push_back(result);
-        cleanup();
-        return fail(c, OVS_ENOMEM, "statistics scratch allocation failed");
-    }
-    owned.push_back(S); owned.push_back(counts); owned.push_back(partial); owned.push_back(result);
-    // GlobalStatistics::MIN_MEASURED = 0.1 s (GlobalStatistics.cc:32, KBRTestApp.cc:502)
-    const int rates = measured_time_s >= 0.1;
-    hipError_t e = launch_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids,
-                                measured_time_s, (uint64_t)c->P.testMsgSize, rates, S, counts,
-                                partial, result, c->num_cu, s);
+    CallFrame F(dev || n == 0, s);                            // an empty batch has nothing to stage
+    const ovs_route_out* dout = F.in(out, n);
+    const uint32_t* ds = F.in(src, n);
+    const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
     StatsDev h{};
     double r[NSTAT * 5];
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(r, result, sizeof r, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    cleanup();
-    if (e != hipSuccess) return hip_fail(c, e, "statistics kernels");
+    const ovs_status st = run_stats(c, F, s, dout, dk, ds, n, lookup_node_ids, measured_time_s,
+                                    (uint64_t)c->P.testMsgSize, nullptr, 0, &h, r);
+    if (st != OVS_OK) return st;
 
     ovs_kbrtest_stats& o = *stats;
     std::memset(&o, 0, sizeof o);
@@ -2457,24 +2182,7 @@ ovs_status ovs_kbrtest_stats_batch(ovs_ctx* c, const ovs_route_out* out, const o
     for (int i = 0; i < 64; ++i) o.hop_hist[i] = h.hist[i];
     ovs_stddev* sd[NSTAT] = {&o.delivered_msgs_per_s, &o.delivered_bytes_per_s, &o.dropped_msgs_per_s,
                              &o.dropped_bytes_per_s, &o.delivery_ratio};
-    for (int k = 0; k < NSTAT; ++k) {
-        const double sum = r[k * 5 + 0], sq = r[k * 5 + 1];
-        uint64_t cnt;
-        std::memcpy(&cnt, &r[k * 5 + 4], sizeof cnt);
-        ovs_stddev& d = *sd[k];
-        d.count = cnt;
-        if (!cnt) continue;
-        // cStdDev::getMean / getVariance (OMNeT++ 4.x): sample variance, 0 below two values or if negative
-        d.mean = sum / (double)cnt;
-        double var = 0.0;
-        if (cnt > 1) {
-            var = (sq - sum * sum / (double)cnt) / (double)(cnt - 1);
-            if (var < 0) var = 0;
-        }
-        d.stddev = std::sqrt(var);
-        d.min = r[k * 5 + 2];
-        d.max = r[k * 5 + 3];
-    }
+    for (int k = 0; k < NSTAT; ++k) finish_stddev(r, k, *sd[k]);
     return OVS_OK;
 }
 
@@ -2491,48 +2199,16 @@ ovs_status ovs_kbrtest_lookup_stats_batch(ovs_ctx* c, const ovs_lookup_out* out,
     HIPCHK(c, hipSetDevice(c->device));
     const bool dev = flags & OVS_DEVICE_PTRS;
     hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    const ovs_route_out* dout = reinterpret_cast<const ovs_route_out*>(out);
-    const K160* dk = reinterpret_cast<const K160*>(keys);
-    const uint32_t* ds = src;
-    const uint32_t* dsib = siblings;
-    std::vector<void*> owned;
-    auto cleanup = [&]() { for (void* p : owned) hipFree(p); };
-    if (!dev && n) {
-        ovs_route_out* o; K160* k = nullptr; uint32_t* r; uint32_t* f; bool ow;
-        ovs_status st = to_device(c, reinterpret_cast<const ovs_route_out*>(out), n, false, &o, &ow);
-        if (st != OVS_OK) return st;
-        owned.push_back(o);
-        st = to_device(c, src, n, false, &r, &ow);
-        if (st != OVS_OK) { cleanup(); return st; }
-        owned.push_back(r);
-        st = to_device(c, siblings, n * (uint64_t)siblings_stride, false, &f, &ow);
-        if (st != OVS_OK) { cleanup(); return st; }
-        owned.push_back(f);
-        if (lookup_node_ids) {
-            st = to_device(c, reinterpret_cast<const K160*>(keys), n, false, &k, &ow);
-            if (st != OVS_OK) { cleanup(); return st; }
-            owned.push_back(k);
-        }
-        dout = o; dk = k; ds = r; dsib = f;
-    }
-    StatsDev* S = nullptr; uint32_t* counts = nullptr; double* partial = nullptr; double* result = nullptr;
-    const bool okm = hipMalloc(&S, sizeof(StatsDev)) == hipSuccess &&
-                     hipMalloc(&counts, sizeof(uint32_t) * 3 * c->n) == hipSuccess &&
-                     hipMalloc(&partial, sizeof(double) * STATS_NODE_BLOCKS * NSTAT * 5) == hipSuccess &&
-                     hipMalloc(&result, sizeof(double) * NSTAT * 5) == hipSuccess;
-    owned.push_back(S); owned.push_back(counts); owned.push_back(partial); owned.push_back(result);
-    if (!okm) { cleanup(); return fail(c, OVS_ENOMEM, "statistics scratch allocation failed"); }
-    const int rates = measured_time_s >= 0.1;      // GlobalStatistics::MIN_MEASURED (KBRTestApp.cc:502)
-    hipError_t e = launch_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids, measured_time_s, 0, rates,
-                                S, counts, partial, result, c->num_cu, s, dsib ? dsib : src,
-                                (uint64_t)siblings_stride);
+    CallFrame F(dev || n == 0, s);                            // an empty batch has nothing to stage
+    const ovs_route_out* dout = F.in(reinterpret_cast<const ovs_route_out*>(out), n);
+    const uint32_t* ds = F.in(src, n);
+    const uint32_t* dsib = F.in(siblings, n * (uint64_t)siblings_stride);
+    const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
     StatsDev h{};
     double r[NSTAT * 5];
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(r, result, sizeof r, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    cleanup();
-    if (e != hipSuccess) return hip_fail(c, e, "statistics kernels");
+    const ovs_status st = run_stats(c, F, s, dout, dk, ds, n, lookup_node_ids, measured_time_s, 0, dsib ? dsib : src,
+                                    (uint64_t)siblings_stride, &h, r);
+    if (st != OVS_OK) return st;
 
     ovs_kbrtest_lookup_stats& o = *stats;
     std::memset(&o, 0, sizeof o);
@@ -2555,26 +2231,9 @@ ovs_status ovs_kbrtest_lookup_stats_batch(ovs_ctx* c, const ovs_lookup_out* out,
     if (n) o.total_latency_mean_s = ((double)h.lat_sum * 1e-9 + (double)h.dropped * failure_latency_s) / (double)n;
     for (int i = 0; i < 8; ++i) o.status_count[i] = h.status[i];
     for (int i = 0; i < 64; ++i) o.hop_hist[i] = h.hist[i];
-    const int slot[3] = {0, 2, 4};
-    ovs_stddev* sd[3] = {&o.successful_lookups_per_s, &o.failed_lookups_per_s, &o.success_ratio};
-    for (int q = 0; q < 3; ++q) {
-        const int k = slot[q];
-        const double sum = r[k * 5 + 0], sq = r[k * 5 + 1];
-        uint64_t cnt;
-        std::memcpy(&cnt, &r[k * 5 + 4], sizeof cnt);
-        ovs_stddev& d = *sd[q];
-        d.count = cnt;
-        if (!cnt) continue;
-        d.mean = sum / (double)cnt;
-        double var = 0.0;
-        if (cnt > 1) {
-            var = (sq - sum * sum / (double)cnt) / (double)(cnt - 1);
-            if (var < 0) var = 0;
-        }
-        d.stddev = std::sqrt(var);
-        d.min = r[k * 5 + 2];
-        d.max = r[k * 5 + 3];
-    }
+    finish_stddev(r, 0, o.successful_lookups_per_s);
+    finish_stddev(r, 2, o.failed_lookups_per_s);
+    finish_stddev(r, 4, o.success_ratio);
     return OVS_OK;
 }
 

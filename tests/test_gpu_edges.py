@@ -53,3 +53,104 @@ def test_source_outside_the_network_is_refused(engine: KbrEngine, overlay):
     again = engine.lookup(keys, src)                     # the context is still usable, results unchanged
     for f in ok:
         assert np.array_equal(ok[f], again[f]), f
+
+
+# Every other host-pointer entry point with a KbrEngine wrapper: one index outside the network is
+# refused on the host, before the call stages anything on the device, and the same valid call before
+# and after the refusal returns identical arrays (a refused call leaves nothing behind that a later
+# one could trip over).  ovs_route_batch / ovs_lookup_batch: test_source_outside_the_network_is_refused.
+
+def _same(a, b):
+    a, b = (a, b) if isinstance(a, tuple) else ((a,), (b,))
+    assert len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _refused_between(call, good, bads, match):
+    ok = call(*good)
+    for bad in bads:
+        with pytest.raises(KbrError, match=match):
+            call(*bad)
+    _same(ok, call(*good))
+
+
+def _batch(net, seed=5, m=100):
+    rng = np.random.default_rng(seed)
+    return W.random_keys(m, rng), rng.integers(0, len(net.ids), m).astype(np.uint32)
+
+
+def _with(a, i, v):
+    b = a.copy()
+    b[i] = v
+    return b
+
+
+@pytest.mark.parametrize("overlay", ["chord", "kademlia"])
+def test_find_node_outside_the_network_is_refused(engine: KbrEngine, overlay):
+    net = _load(engine, overlay)
+    keys, node = _batch(net)
+    _refused_between(lambda nd: engine.findNode(nd, keys, 4, 1), (node,),
+                     [(_with(node, 57, bad),) for bad in (len(net.ids), 0xFFFFFFFF)], "node index out of range")
+
+
+def test_delay_outside_the_network_is_refused(engine: KbrEngine):
+    net = _load(engine, "chord")
+    _, a = _batch(net, 5)
+    _, b = _batch(net, 6)
+    nbytes = np.full(100, 100, np.int32)
+    _refused_between(lambda x, y: engine.delay_ns(x, y, nbytes), (a, b),
+                     [(_with(a, 57, len(net.ids)), b), (a, _with(b, 99, 0xFFFFFFFF))], "node index out of range")
+
+
+def test_koorde_find_node_outside_the_network_is_refused(engine: KbrEngine):
+    net = _load(engine, "koorde")
+    keys, node = _batch(net)
+    _refused_between(lambda nd: engine.koorde_find_node(nd, keys), (node,),
+                     [(_with(node, 0, len(net.ids)),), (_with(node, 99, 0xFFFFFFFF),)], "node index out of range")
+
+
+def test_epichord_find_node_outside_the_network_is_refused():
+    from epichord_snap import make_queries, make_snapshot
+    snap = make_snapshot(500, 31, list_size=4)
+    node, keys, src, now = make_queries(snap, 100, 32)
+    n = snap["n"]
+    with KbrEngine(0) as eng:
+        eng.set_params(Params.epichord().replace(successorListSize=snap["L"], cacheTTL=snap["cache_ttl_param"] / 10**9))
+        eng.epichord_load(snap["ids"], np.zeros((n, 2)), snap["succ"], snap["nsucc"], snap["pred"], snap["npred"],
+                          snap["full"], snap["cache_off"], snap["cache_node"], snap["cache_last"], snap["cache_ttl"])
+        _refused_between(lambda nd, sr: eng.epichord_find_node(nd, keys, sr, now, 3), (node, src),
+                         [(_with(node, 57, n), src), (node, _with(src, 57, 0xFFFFFFFE))], "index out of range")
+
+
+def test_refresh_lookups_outside_the_network_are_refused(engine: KbrEngine):
+    net = _load(engine, "kademlia")
+    keys, src = _batch(net)
+
+    def call(s, record):
+        r = engine.kad_refresh(keys, s, 8, record=record)
+        return tuple(r[f] for f in sorted(r))
+
+    for record in (True, False):      # responders in the caller's arrays / in the context's cached buffer
+        _refused_between(call, (src, record), [(_with(src, 57, bad), record) for bad in (len(net.ids), 0xFFFFFFFF)],
+                         "source index out of range")
+
+
+def test_refresh_keys_outside_the_network_are_refused(engine: KbrEngine):
+    net = _load(engine, "kademlia")
+    nodes = np.arange(0, len(net.ids), 5, dtype=np.uint32)
+    _refused_between(engine.kad_refresh_keys, (nodes,),
+                     [(_with(nodes, 57, bad),) for bad in (len(net.ids), 0xFFFFFFFF)], "node index out of range")
+
+
+def test_statistics_refusal_leaves_results_unchanged(engine: KbrEngine):
+    """The statistics kernels skip a source outside the network themselves (stats.hip), so neither call
+    refuses one; their host-side refusal is the measured time."""
+    net = _load(engine, "kademlia")
+    keys, src = _batch(net)
+    r, lc = engine.lookup(keys, src), engine.lookupCall(keys, src)
+    for stats, res in ((engine.kbrtest_stats, r), (engine.kbrtest_lookup_stats, lc)):
+        ok = bytes(stats(res, keys, src, 120.0))
+        with pytest.raises(KbrError, match="measured_time_s must be >= 0"):
+            stats(res, keys, src, -1.0)
+        with pytest.raises(KbrError, match="measured_time_s must be >= 0"):
+            stats(res, keys, src, float("nan"))
+        assert bytes(stats(res, keys, src, 120.0)) == ok

@@ -61,3 +61,20 @@ def test_host_table_bookkeeping_clean_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_call_frame_clean_under_asan_ubsan(tmp_path):
+    """The C ABI's per-call device memory (oversim_amd/csrc/call_frame.hpp: the call frame, the
+    event-ordered cached buffer and the counter slots) built with plain g++ under ASan/UBSan -Werror
+    against a fake HIP runtime whose every call is made to fail in turn: each failure is reported,
+    nothing leaks, every lease records its event, and a device-pointer frame calls nothing
+    (tests/call_frame_driver.cpp).  No HIP library is linked."""
+    exe = tmp_path / "call_frame_driver"
+    c = ["g++", "-std=c++17", *SAN, *WARN, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include",
+         "-I", str(ROOT / "oversim_amd" / "csrc"), str(ROOT / "tests" / "call_frame_driver.cpp"), "-o", str(exe)]
+    r = subprocess.run(c, capture_output=True, text=True)
+    assert r.returncode == 0, f"{' '.join(c)}\n{r.stdout}{r.stderr}"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
