@@ -526,6 +526,43 @@ ovs_status  ovs_kbrtest_lookup_stats_batch(ovs_ctx* ctx, const ovs_lookup_out* o
                                            double failure_latency_s, ovs_kbrtest_lookup_stats* stats,
                                            uint32_t flags, void* stream);
 
+/* ---- Chord overlay broadcast (additive to ABI 12; test OVS_HAS_CHORD_BROADCAST) ----
+ * Replaces, for a batch of broadcasts on a converged ring (ovs_chord_load):
+ *   BroadcastTestApp::initBroadcast / rpcBroadcastRequest  src/tier2/broadcasttestapp/BroadcastTestApp.cc:197-340
+ *   Chord::forwardBroadcast                                 src/overlay/chord/Chord.cc:1410-1445
+ *   SimpleNodeEntry::calcDelay with the sender's transmit queue  SimpleNodeEntry.cc:164-183
+ * Broadcast b starts at node initiators[b] at time 0 with TTL = ttl and a query of query_bytes
+ * characters.  A node that receives the request with TTL > 0 splits its part of the ring among its
+ * fingers (highest first, then successor 0) and sends each a request with TTL - 1; the j-th of them
+ * leaves after j + 1 serialisation times.  No DHT items are stored (no BroadcastResponseCall). */
+#define OVS_HAS_CHORD_BROADCAST 1
+typedef struct ovs_bcast_node {   /* 16 B, one per (broadcast, node) */
+    int64_t  arrival_ns;          /* -1: not reached (ttl ran out above it) */
+    uint32_t parent;              /* 0xFFFFFFFF at the initiator and when not reached */
+    uint16_t hops;                /* ttl - TTL on arrival; 0 when not reached */
+    uint16_t rank;                /* j: position in the parent's request list; 0 at the initiator / not reached */
+} ovs_bcast_node;
+typedef struct ovs_bcast_stats {  /* one per broadcast: GlobalStatistics::bcastSearch + RECORD_STATS */
+    uint64_t expected;            /* globalNodeList->getNumNodes() */
+    uint64_t actual;              /* nodes that forwarded (received with TTL > 0) */
+    uint64_t expired;             /* nodes that received TTL <= 0 */
+    uint64_t messages;            /* numMessages: forwarded calls + responses */
+    uint64_t bytes;               /* numBytes: the calls' own lengths + the responses' (an expired node's counts 0) */
+    int64_t  last_arrival_ns;
+    ovs_stddev hop_count;         /* "Broadcast: Hop count" */
+} ovs_bcast_stats;
+/* initiators[nb] and nodes[nb * n] (broadcast-major; may be NULL) follow `flags`; stats[nb] (may be
+ * NULL) is host memory.  The level loop runs on the host and reads each level's size back, so the
+ * call has completed on `stream` when it returns, in both pointer modes.  OVS_EINVAL: an initiator
+ * outside the network, ttl outside 0..65535, query_bytes < 0 (checked before anything is staged;
+ * device-pointer initiators are checked on the device and skipped); OVS_ENOTSUP: explicit tables
+ * (ovs_chord_load_tables: ranges overlap there and the first arrival in time decides who
+ * forwards, which needs a time-ordered replay) and arcs of a sharded ring; OVS_ESTATE: another
+ * overlay or no network. */
+ovs_status  ovs_chord_broadcast_batch(ovs_ctx* ctx, const uint32_t* initiators, uint64_t nb, int32_t ttl,
+                                      int32_t query_bytes, ovs_bcast_node* nodes, ovs_bcast_stats* stats,
+                                      uint32_t flags, void* stream);
+
 /* ---- multi-GPU sharding (one process per GPU; the host exchanges records) ----
  * The sorted ring is cut into contiguous arcs, one per rank.  Node keys,
  * coordinates and 64 B node records are replicated; the finger rows -- the bulk

@@ -133,6 +133,8 @@ assert KOORDE_EXT_DTYPE.itemsize == 28
 LOOKUP_OUT_DTYPE = np.dtype([("num_siblings", "<u4"), ("hops", "<u2"), ("status", "u1"),
                              ("is_valid", "u1"), ("latency_ns", "<i8")])
 assert LOOKUP_OUT_DTYPE.itemsize == 16
+BCAST_NODE_DTYPE = np.dtype([("arrival_ns", "<i8"), ("parent", "<u4"), ("hops", "<u2"), ("rank", "<u2")])
+assert BCAST_NODE_DTYPE.itemsize == 16
 
 class StdDev(C.Structure):
     """ovs_stddev: one cStdDev summary (GlobalStatistics::addStdDev)."""
@@ -163,6 +165,14 @@ class KbrTestStats(C.Structure):
         "dropped_bytes_per_s": "KBRTestApp: One-way Dropped Bytes/s",
         "delivery_ratio": "KBRTestApp: One-way Delivery Ratio",
     }
+
+
+class BcastStats(C.Structure):
+    """ovs_bcast_stats: one broadcast (GlobalStatistics::bcastSearch and BroadcastTestApp's RECORD_STATS)."""
+
+    _fields_ = [("expected", C.c_uint64), ("actual", C.c_uint64), ("expired", C.c_uint64),
+                ("messages", C.c_uint64), ("bytes", C.c_uint64), ("last_arrival_ns", C.c_int64),
+                ("hop_count", StdDev)]
 
 
 _lib = None
@@ -223,6 +233,7 @@ def lib() -> C.CDLL:
         "ovs_find_node_batch": ([vp, vp, vp, u64, i32, i32, vp, u32, vp, vp, u32, vp], C.c_int),
         "ovs_delay_batch": ([vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
         "ovs_sync": ([vp], C.c_int),
+        "ovs_chord_broadcast_batch": ([vp, vp, u64, i32, i32, vp, vp, u32, vp], C.c_int),
         "ovs_kbrtest_stats_batch": ([vp, vp, vp, vp, u64, C.c_double, i32, vp, u32, vp], C.c_int),
         "ovs_chord_fix_fingers": ([vp, vp, u64, vp], C.c_int),
         "ovs_lookup_batch": ([vp, vp, vp, u64, i32, vp, vp, u32, vp], C.c_int),
@@ -302,6 +313,12 @@ class KbrTestLookupStats(C.Structure):
         "failed_lookups_per_s": "KBRTestApp: Failed Lookups/s",
         "success_ratio": "KBRTestApp: Lookup Success Ratio",
     }
+
+
+def bcast_stats_dict(st: BcastStats) -> dict:
+    d = {f: getattr(st, f) for f, _ in BcastStats._fields_ if f != "hop_count"}
+    d["hop_count"] = {f: getattr(st.hop_count, f) for f, _ in StdDev._fields_}
+    return d
 
 
 class KbrEngine:
@@ -672,6 +689,29 @@ class KbrEngine:
         self._chk(self._L.ovs_delay_batch(self._h, _ptr(a), _ptr(b), _ptr(nbytes), len(a), _ptr(out), 0, None),
                   "ovs_delay_batch")
         return out
+
+    def chord_broadcast(self, initiators, ttl: int = 100, query_bytes: int = 0, nodes: bool = True):
+        """Batched overlay broadcasts on a converged Chord ring (ovs_chord_broadcast_batch:
+        BroadcastTestApp::rpcBroadcastRequest over Chord::forwardBroadcast, Chord.cc:1410-1445), one
+        from each initiator.  Returns (records, stats): records (nb, n) of BCAST_NODE_DTYPE (None with
+        nodes=False) and one dict per broadcast (ovs_bcast_stats; hop_count = the cStdDev fields)."""
+        init = np.ascontiguousarray(initiators, dtype=np.uint32)
+        nb = len(init)
+        rec = np.empty((nb, self.n), dtype=BCAST_NODE_DTYPE) if nodes else None
+        st = (BcastStats * max(nb, 1))()
+        self._chk(self._L.ovs_chord_broadcast_batch(self._h, _ptr(init), nb, int(ttl), int(query_bytes), _ptr(rec),
+                                                    C.cast(st, C.c_void_p), 0, None), "ovs_chord_broadcast_batch")
+        return rec, [bcast_stats_dict(st[b]) for b in range(nb)]
+
+    def chord_broadcast_device(self, init_ptr: int, nb: int, ttl: int, query_bytes: int, nodes_ptr: int | None,
+                               stream: int | None = None):
+        """The same for device-resident initiators / records (the call completes on `stream`); returns the stats."""
+        st = (BcastStats * max(nb, 1))()
+        self._chk(self._L.ovs_chord_broadcast_batch(self._h, C.c_void_p(init_ptr), nb, int(ttl), int(query_bytes),
+                                                    C.c_void_p(nodes_ptr) if nodes_ptr else None,
+                                                    C.cast(st, C.c_void_p), DEVICE_PTRS,
+                                                    C.c_void_p(stream) if stream else None), "ovs_chord_broadcast_batch")
+        return [bcast_stats_dict(st[b]) for b in range(nb)]
 
     def sync(self):
         self._chk(self._L.ovs_sync(self._h), "ovs_sync")
