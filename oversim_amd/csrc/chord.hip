@@ -17,6 +17,7 @@
 
 #include "engine.hpp"
 #include "launch.hpp"
+#include "persist.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -507,7 +508,7 @@ struct LaneIO {
     ovs_done_rec* __restrict__ stage_done;
     uint8_t* __restrict__ stag;            // arc of the hand-off, or nsh: finished
     // dynamic tail (dyn != nullptr; routes and shard steps): each wave's static slice covers [0, dyn_from);
-    // the rest is handed out K1_DYN_CH lookups at a time from the zeroed counter *dyn
+    // the rest is handed out K1_TUNE.dyn_chunk lookups at a time from the zeroed counter *dyn (persist.hpp)
     unsigned long long* dyn;
     uint64_t dyn_from;
 };
@@ -515,28 +516,10 @@ struct LaneIO {
 // Persistent waves finish their static slices up to a quarter of the kernel apart (a census of
 // their exit times, -DOVS_K1_TAIL): the last ~30 % of a batch is handed out dynamically instead, in
 // chunks of one refill, so that the waves that run ahead take more
-#ifndef K1_DYN_CH
-#define K1_DYN_CH 64
-#endif
-#ifndef K1_DYN_STATIC
-#define K1_DYN_STATIC 0.70
-#endif
+constexpr PersistTune K1_TUNE{0.70, 64};
 
 #ifdef OVS_K1_TAIL
-// tail census (-DOVS_K1_TAIL builds): each wave's start and exit on the 100 MHz real-time clock, so
-// the spread of the persistent waves' finishing times (the kernel's tail) can be read off one launch
-constexpr int K1_TAIL_MAX = 1 << 16;
-__device__ unsigned long long g_k1_tail[2 * K1_TAIL_MAX];
-// lane 0 of the wave records the real-time counter in slot 2 * wave + which; the slot comes from
-// wave-uniform values, so nothing stays live across the kernel's loop (a first version that kept the
-// wave index and the start time live spilled the kernel)
-__device__ __forceinline__ void ovs_tail_mark(unsigned long long* arr, int max, int which)
-{
-    const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
-    const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wib;
-    const unsigned long long t = wall_clock64();
-    if (__lane_id() == 0 && w < (uint64_t)max) arr[2 * w + which] = t;
-}
+__device__ unsigned long long g_k1_tail[2 * PERSIST_TAIL_MAX];   // the tail census (persist.hpp)
 #endif
 #ifdef OVS_CHORD_STATS
 // lines consumed by kind: [0] FETCH, [1] START, [2] NODE, [3] first probe of a hop, [4] a further probe
@@ -623,13 +606,9 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
     // requests its source's NodeRec in the refill iteration itself (its key is loaded there too,
     // used from the next iteration on) -- one iteration per lookup fewer than requesting the line
     // in a PH_FETCH iteration after the refill.
-#ifdef OVS_K1_NO_PRELOAD
-    constexpr bool pre_ok = false;    // A/B build: the PH_FETCH iteration for every lookup
-#else
     // (the shard step keeps the PH_FETCH iteration: a preloaded source spills 20 B per lane at 5
     // waves/SIMD even with its outcomes staged where decided)
     constexpr bool pre_ok = !SHARD;
-#endif
     const K160* const pkeys = SHARD ? io.fkeys : io.qkeys;
     const uint32_t* const psrc = SHARD ? io.fsrc : io.qsrc;
     uint32_t pS = 0;
@@ -653,13 +632,10 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
         const uint64_t need = __ballot(!active);
         if (more && need != 0 && cursor >= end) {
             // the static slice is spent: the next dynamic chunk (one atomic a chunk, lane 0)
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(io.dyn, (unsigned long long)K1_DYN_CH);
-            const uint64_t nb = io.dyn_from + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                                               (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+            const uint64_t nb = persist_claim_chunk<K1_TUNE.dyn_chunk>(io.dyn, io.dyn_from, lane);
             if (nb < io.n) {
                 cursor = nb;
-                end = min(nb + (uint64_t)K1_DYN_CH, io.n);
+                end = min(nb + (uint64_t)K1_TUNE.dyn_chunk, io.n);
                 preload(cursor);
             } else {
                 more = false;
@@ -1077,7 +1053,7 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
         }
     }
 #ifdef OVS_K1_TAIL
-    ovs_tail_mark(g_k1_tail, K1_TAIL_MAX, 1);
+    ovs_tail_mark(g_k1_tail, PERSIST_TAIL_MAX, 1);
 #endif
 }
 
@@ -1252,40 +1228,17 @@ hipError_t launch_chord_export(const KeyRec* recs, const FingerEnt* fingers, uin
 }
 
 // occupancy-sized persistent grid: every resident wave owns one contiguous slice of the work
-template <class Kern>
-static uint64_t persistent_chunk(Kern k, int* cache, uint64_t n, int num_cu, uint64_t* blocks)
-{
-    if (*cache == 0) {
-        int b = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k, 256, 0) != hipSuccess || b < 1) b = 1;
-        *cache = b;
-    }
-    const uint64_t waves = (uint64_t)num_cu * (uint64_t)(*cache) * 4;   // 4 waves per block
-    uint64_t chunk = (n + waves - 1) / waves;
-    if (chunk < 1) chunk = 1;
-    const uint64_t need_waves = (n + chunk - 1) / chunk;
-    *blocks = (need_waves + 3) / 4;
-    return chunk;
-}
-
+// (persist.hpp), with the dynamic tail when the caller brought a counter
 template <bool REC, bool RECORD, bool SHARD, bool LKC = false, bool DEF = false>
 static hipError_t lanes_launch(const ChordView& V, const DelayConsts& DC, const LookupConsts& LC, LaneIO io,
                                int num_cu, hipStream_t s)
 {
-    static int bpc = 0;
-    uint64_t blocks = 0;
-    io.chunk = persistent_chunk(k_chord_lanes<REC, RECORD, SHARD, LKC, DEF>, &bpc, io.n, num_cu, &blocks);
-    if (io.dyn) {
-        // static slices cover K1_DYN_STATIC of the batch, the rest goes out in chunks (tiny batches: static)
-        const uint64_t waves = blocks * 4;
-        const uint64_t cs = (uint64_t)((double)io.n * K1_DYN_STATIC) / waves;
-        if (cs < (uint64_t)K1_DYN_CH) {
-            io.dyn = nullptr;
-        } else {
-            io.chunk = cs;
-            io.dyn_from = cs * waves;
-        }
-    }
+    const PersistPlan pl = persist_plan(io.n, persist_waves<k_chord_lanes<REC, RECORD, SHARD, LKC, DEF>>(num_cu),
+                                        io.dyn != nullptr, K1_TUNE);
+    const uint64_t blocks = pl.blocks;
+    io.chunk = pl.chunk;
+    io.dyn_from = pl.dyn_from;
+    if (!pl.dyn) io.dyn = nullptr;
 #ifdef OVS_CHORD_STATS
     unsigned long long z[8] = {};
     hipMemcpyToSymbolAsync(HIP_SYMBOL(g_k1_stats), z, sizeof z, 0, hipMemcpyHostToDevice, s);
@@ -1293,22 +1246,7 @@ static hipError_t lanes_launch(const ChordView& V, const DelayConsts& DC, const 
     hipLaunchKernelGGL((k_chord_lanes<REC, RECORD, SHARD, LKC, DEF>), dim3((unsigned)blocks), dim3(256), 0, s, V, DC,
                        LC, io);
 #ifdef OVS_K1_TAIL
-    if (!SHARD) {
-        const uint64_t nw = blocks * 4 < (uint64_t)K1_TAIL_MAX ? blocks * 4 : (uint64_t)K1_TAIL_MAX;
-        std::vector<unsigned long long> tt(2 * nw);
-        hipMemcpyFromSymbolAsync(tt.data(), HIP_SYMBOL(g_k1_tail), sizeof(unsigned long long) * 2 * nw, 0,
-                                 hipMemcpyDeviceToHost, s);
-        hipStreamSynchronize(s);
-        unsigned long long t0 = ~0ull;
-        std::vector<double> fin;
-        for (uint64_t w = 0; w < nw; ++w) t0 = tt[2 * w + 1] < t0 ? tt[2 * w + 1] : t0;
-        for (uint64_t w = 0; w < nw; ++w) fin.push_back((double)(tt[2 * w + 1] - t0) * 0.01);   // 100 MHz -> us
-        std::sort(fin.begin(), fin.end());
-        auto pct = [&](double f) { return fin[(size_t)(f * (fin.size() - 1))]; };
-        fprintf(stderr, "k1tail waves=%llu chunk=%llu finish_us_after_first_exit p0=%.1f p10=%.1f p50=%.1f p90=%.1f p99=%.1f max=%.1f\n",
-                (unsigned long long)nw, (unsigned long long)io.chunk, pct(0), pct(0.1), pct(0.5), pct(0.9), pct(0.99),
-                fin.back());
-    }
+    if (!SHARD) persist_tail_report("k1tail", HIP_SYMBOL(g_k1_tail), blocks * 4, io.chunk, s);
 #endif
 #ifdef OVS_CHORD_STATS
     hipMemcpyFromSymbolAsync(z, HIP_SYMBOL(g_k1_stats), sizeof z, 0, hipMemcpyDeviceToHost, s);
@@ -1334,18 +1272,15 @@ static hipError_t chord_route_launch(const ChordView& V, const DelayConsts& DC, 
             if (DC.lookupCall) return lanes_launch<false, false, false, true>(V, DC, LC, io, num_cu, s);
         }
         if (DC.lookupCall) return hipErrorNotSupported;
-#ifndef OVS_K1_NO_DEF
         if constexpr (!REC && !RECORD) {
             if (V.ns == 8 && LC.hopCountMax == 50) return lanes_launch<false, false, false, false, true>(V, DC, LC, io, num_cu, s);
         }
-#endif
         return lanes_launch<REC, RECORD, false>(V, DC, LC, io, num_cu, s);
     } else {
-        static int bpc = 0;
-        uint64_t blocks = 0;
-        const uint64_t chunk = persistent_chunk(k_chord_route<false, RECORD, REC>, &bpc, nq, num_cu, &blocks);
-        hipLaunchKernelGGL((k_chord_route<false, RECORD, REC>), dim3((unsigned)blocks), dim3(256), 0, s, V, DC, LC,
-                           qkeys, qsrc, nq, chunk, out, hopseq);
+        // explicit tables: static slices only
+        const PersistPlan pl = persist_plan(nq, persist_waves<k_chord_route<false, RECORD, REC>>(num_cu), false, K1_TUNE);
+        hipLaunchKernelGGL((k_chord_route<false, RECORD, REC>), dim3((unsigned)pl.blocks), dim3(256), 0, s, V, DC, LC,
+                           qkeys, qsrc, nq, pl.chunk, out, hopseq);
         return hipGetLastError();
     }
 }
@@ -1578,9 +1513,7 @@ hipError_t launch_chord_shard_step(const ChordView& V, const DelayConsts& DC, co
     // DC.lookupCall: a LookupCall batch (the responsible node's larger answer, no route message)
     e = LC.recursive ? lanes_launch<true, false, true>(V, DC, LC, io, num_cu, s)
         : DC.lookupCall ? lanes_launch<false, false, true, true>(V, DC, LC, io, num_cu, s)
-#ifndef OVS_K1_NO_DEF
                         : (V.ns == 8 && LC.hopCountMax == 50) ? lanes_launch<false, false, true, false, true>(V, DC, LC, io, num_cu, s)
-#endif
                         : lanes_launch<false, false, true>(V, DC, LC, io, num_cu, s);
     if (e != hipSuccess) return e;
     // outcomes to their outputs: class d < nsh = hand-offs to arc d (segment d of out), nsh = done

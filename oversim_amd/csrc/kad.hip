@@ -468,16 +468,12 @@ __device__ __forceinline__ uint32_t kb_nth_bit256(uint64_t z0, uint64_t z1, uint
     return base + pos;
 }
 
-// the row blocks' 16 B stores (OVS_KB_NT: non-temporal, so the 29 GB of rows a 2^24 build writes
-// do not displace the 128 MB top-key array the member gathers read from the MALL -- an A/B build)
+// the row blocks' 16 B stores (plain: non-temporal ones, so that the 29 GB of rows a 2^24 build writes
+// do not displace the 128 MB top-key array the member gathers read from the MALL, measured slower)
 typedef unsigned int kb_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void kb_store(kb_u4* p, kb_u4 v)
 {
-#ifdef OVS_KB_NT
-    __builtin_nontemporal_store(v, p);
-#else
     *p = v;
-#endif
 }
 
 // bucket m > endIndex of node v under the snapshot rule: up to k members of T_m chosen

@@ -187,8 +187,9 @@ struct KadExhTrace {
 hipError_t kad_exhaustive(const KadTables& t, const double2* xy, uint32_t n, const ovs_params& P, const DelayConsts& DC,
                           int R, int ns, bool oneway, const K160* qkeys, const uint32_t* qsrc, uint64_t nq, void* out,
                           uint32_t* sibs, uint32_t* responders, int64_t* rtts, uint32_t* rpcs, int num_cu,
-                          hipStream_t st, bool* capacity_error, const KadExhTrace* trace = nullptr, bool pad = true,
-                          bool internal_resp = false);
+                          hipStream_t st, bool dyn_tail, bool* capacity_error, const KadExhTrace* trace = nullptr,
+                          bool pad = true, bool internal_resp = false);
+// dyn_tail: the batch's tail may go out in dynamic chunks (persist.hpp; false: static slices only)
 // pad = false: the responder / RTT rows are left unwritten past a lookup's responders (the caller
 // filled them, or reads only the lookup's hops entries -- the internal visited lists)
 // internal_resp: nobody reads the responder rows (they are the lookups' visited sets): the first

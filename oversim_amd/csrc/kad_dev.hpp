@@ -488,11 +488,7 @@ __device__ __forceinline__ int kad_find_node_blk(const KadView& V, uint32_t c, c
         if (cnt) {
             // a block holding one entry at its start (a sibling row's last block: 9 entries at s = 8)
             // is sorted and enters the result by one insertion
-#ifdef OVS_KAD_NO_INSERT1
-            const bool one = false;                  // A/B: the round-3 sort + merge for every block
-#else
             const bool one = cnt == 1 && b.x[0] != NONE;
-#endif
             if (!one) blk_sort8<false, EX>(b, K, V.nodes);
             if (seen == 0) blk_assign(res, b);       // into an empty result the merge is the sorted block itself
             else if (one) blk_insert1<EX, C>(res, b.d[0], b.x[0], K, V.nodes);

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <mutex>
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,7 @@ __device__ unsigned long long g_kx_stats[16];
 #endif
 
 #include "kad_dev.hpp"
+#include "persist.hpp"
 
 namespace ovs {
 
@@ -755,16 +757,11 @@ __device__ __forceinline__ XCfg kad_def_cfg(XCfg C)
     return C;
 }
 
-// the dynamic tail (as K1's and K2's): static slices cover KX_DYN_STATIC of the batch, the rest goes
-// out KX_DYN_CH lookups at a time from a zeroed counter at the front of the lanes' scratch.  The
+// the dynamic tail (persist.hpp): static slices cover KX_TUNE.static_share of the batch, the rest goes
+// out KX_TUNE.dyn_chunk lookups at a time from a zeroed counter at the front of the lanes' scratch.  The
 // exhaustive lookups run long (17 RPCs each on R), so smaller chunks and a larger dynamic share than
 // K1's: R 5.34 (0.7, 32) -> 5.24 ms (0.4, 16), profiles/r06_dyn/tune_kx.txt
-#ifndef KX_DYN_CH
-#define KX_DYN_CH 16
-#endif
-#ifndef KX_DYN_STATIC
-#define KX_DYN_STATIC 0.40
-#endif
+constexpr PersistTune KX_TUNE{0.40, 16};
 template <bool EX, bool REG, int XA, bool TR, bool DEF = false>
 __global__ __launch_bounds__(256, REG ? OVS_KX_WAVES : 1) void k_kad_refresh(KadView V, DelayConsts DC, XCfg C0, XScratch X,
                                                      const K160* __restrict__ qkeys, const uint32_t* __restrict__ qsrc,
@@ -780,7 +777,7 @@ __global__ __launch_bounds__(256, REG ? OVS_KX_WAVES : 1) void k_kad_refresh(Kad
     const uint64_t wave = lane >> 6;
     uint64_t cursor = wave * chunk;
     uint64_t end = min(cursor + chunk, dyn ? dyn_from : nq);
-    bool more = dyn != nullptr;       // the dynamic tail (as K2's): chunks of KX_DYN_CH may be left
+    bool more = dyn != nullptr;       // the dynamic tail: chunks of KX_TUNE.dyn_chunk may be left
     const uint64_t lt_mask = (wl == 0) ? 0ull : (~0ull >> (64 - wl));
     bool active = false;
     uint64_t q = 0;
@@ -792,23 +789,16 @@ __global__ __launch_bounds__(256, REG ? OVS_KX_WAVES : 1) void k_kad_refresh(Kad
     // the sources of the wave's next 64 lookups, preloaded one per lane: a refilled lane's first
     // loads (its coordinates, its own KadNode and rows for the start's findNode) wait for nothing
     // loaded in the same iteration
-#ifdef OVS_KX_NO_PRELOAD
-    constexpr bool pre_ok = false;    // A/B build
-#else
     constexpr bool pre_ok = true;
-#endif
     uint32_t pS = 0;
     if (pre_ok && cursor + (uint64_t)wl < end) pS = qsrc[cursor + wl];
     while (true) {
         const uint64_t need = __ballot(!active);
         if (more && need != 0 && cursor >= end) {
-            unsigned long long b = 0;
-            if (wl == 0) b = atomicAdd(dyn, (unsigned long long)KX_DYN_CH);
-            const uint64_t nb = dyn_from + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                                            (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+            const uint64_t nb = persist_claim_chunk<KX_TUNE.dyn_chunk>(dyn, dyn_from, wl);
             if (nb < nq) {
                 cursor = nb;
-                end = min(nb + (uint64_t)KX_DYN_CH, nq);
+                end = min(nb + (uint64_t)KX_TUNE.dyn_chunk, nq);
                 if (pre_ok && cursor + (uint64_t)wl < end) pS = qsrc[cursor + wl];
             } else {
                 more = false;
@@ -923,7 +913,8 @@ size_t g_scratch_cap[64] = {};
 hipError_t kad_exhaustive(const KadTables& t, const double2* xy, uint32_t n, const ovs_params& P, const DelayConsts& DC,
                           int R, int ns, bool oneway, const K160* qkeys, const uint32_t* qsrc, uint64_t nq, void* out,
                           uint32_t* sibs, uint32_t* responders, int64_t* rtts, uint32_t* rpcs, int num_cu,
-                          hipStream_t st, bool* capacity_error, const KadExhTrace* trace, bool pad, bool internal_resp)
+                          hipStream_t st, bool dyn_tail, bool* capacity_error, const KadExhTrace* trace, bool pad,
+                          bool internal_resp)
 {
     *capacity_error = false;
     if (nq == 0) return hipSuccess;
@@ -936,11 +927,7 @@ hipError_t kad_exhaustive(const KadTables& t, const double2* xy, uint32_t n, con
     C.R = R; C.ns = ns; C.alpha = A; C.hcm = P.hopCountMax; C.k = t.k;
     C.oneway = oneway ? 1 : 0;
     C.pad = pad ? 1 : 0;
-#ifdef OVS_KX_NO_LVIS
-    C.lvis = 0;                       // A/B build: every responder to the HBM row
-#else
     C.lvis = internal_resp && !trace ? 1 : 0;
-#endif
     C.strict = P.lookupStrictParallelRpcs; C.visitOnlyOnce = P.lookupVisitOnlyOnce;
     C.newOnResp = P.lookupNewRpcOnEveryResponse; C.newOnTimeout = P.lookupNewRpcOnEveryTimeout;
     C.finishOnFirst = P.lookupFinishOnFirstUnchanged;
@@ -949,103 +936,69 @@ hipError_t kad_exhaustive(const KadTables& t, const double2* xy, uint32_t n, con
     // 2R <= 16: the LookupVector lives in registers and findNode results in sorting-network blocks
     // (the start's own findNode answers k nodes: k = 16, KademliaLarge, takes the scratch form)
     const bool reg = R <= 8 && t.k <= 8;
-    // one lane per lookup, as many lanes as are resident at once (occupancy-sized grid); the
-    // scratch is sized for the lanes
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess || dev < 0 || dev >= 64) return e != hipSuccess ? e : hipErrorInvalidDevice;
-    // the occupancy of each instantiation, per device, filled under the scratch mutex
-    static int bpc[64][32] = {};
     const bool a8 = A > 4;     // the 8-slot instantiations serve lookupParallelRpcs 5..8
     const bool tr = trace != nullptr;
     // the default configuration's instantiation (register LookupVector, no trace, <= 4 slots)
-#ifdef OVS_KX_NO_DEF
-    const bool def = false;          // A/B build: the generic instantiation
-#else
     const bool def = reg && !tr && !a8 && !t.exact && kad_is_def_cfg(C);
-#endif
-    const int ki = (t.exact ? 2 : 0) + (reg ? 1 : 0) + (a8 ? 4 : 0) + (tr ? 8 : 0) + (def ? 16 : 0);
-    std::unique_lock<std::mutex> lock(g_scratch_mu);
-    if (bpc[dev][ki] == 0) {
-        int b = 0;
-        hipError_t oe;
-#define KOCC(ex, rg, xa) (tr ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_kad_refresh<ex, rg, xa, true>, 256, 0) \
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_kad_refresh<ex, rg, xa, false>, 256, 0))
-        if (a8) {
-            if (t.exact) oe = reg ? KOCC(true, true, 8) : KOCC(true, false, 8);
-            else oe = reg ? KOCC(false, true, 8) : KOCC(false, false, 8);
-        } else {
-            if (t.exact) oe = reg ? KOCC(true, true, 4) : KOCC(true, false, 4);
-            else if (def) oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_kad_refresh<false, true, 3, false, true>, 256, 0);
-            else oe = reg ? KOCC(false, true, 4) : KOCC(false, false, 4);
-        }
-#undef KOCC
-        bpc[dev][ki] = (oe == hipSuccess && b > 0) ? b : 1;
-    }
-#ifndef OVS_KX_OVERSUB
-#define OVS_KX_OVERSUB 1
-#endif
-    // OVS_KX_OVERSUB > 1 (A/B builds): that many lanes per resident slot, each wave a shorter slice
-    uint64_t lanes = (uint64_t)num_cu * (uint64_t)bpc[dev][ki] * 256 * OVS_KX_OVERSUB;
-    if (lanes > nq) lanes = nq;
-    lanes = (lanes + 255) / 256 * 256;
-    const uint64_t nhE = reg ? 0 : 2ull * R, resE = reg ? 0 : (uint64_t)(R > t.k ? R : t.k);
-    const uint64_t bytes = 8 + lanes * (nhE * (4 + 8 + 1) + resE * (4 + 8) + XMAXDEAD * 4) + 4;
-    if (g_scratch_cap[dev] < bytes) {
-        if (g_scratch[dev]) { hipDeviceSynchronize(); hipFree(g_scratch[dev]); }
-        g_scratch[dev] = nullptr; g_scratch_cap[dev] = 0;
-        if ((e = hipMalloc(reinterpret_cast<void**>(&g_scratch[dev]), bytes)) != hipSuccess) return e;
-        g_scratch_cap[dev] = bytes;
-    }
-    char* buf = g_scratch[dev];
-    XScratch X;
-    unsigned long long* dyn = reinterpret_cast<unsigned long long*>(buf);   // the dynamic tail's counter
-    char* p = buf + 8;
-    X.nh_d = reinterpret_cast<uint64_t*>(p); p += lanes * nhE * 8;
-    X.res_d = reinterpret_cast<uint64_t*>(p); p += lanes * resE * 8;
-    X.nh_idx = reinterpret_cast<uint32_t*>(p); p += lanes * nhE * 4;
-    X.res_idx = reinterpret_cast<uint32_t*>(p); p += lanes * resE * 4;
-    X.dead = reinterpret_cast<uint32_t*>(p); p += lanes * XMAXDEAD * 4;
-    uint32_t* err = reinterpret_cast<uint32_t*>(p); p += 4;
-    X.nh_used = reinterpret_cast<uint8_t*>(p);
-    X.lanes = lanes;
-    hipMemsetAsync(err, 0, 4, st);
-    const unsigned blocks = (unsigned)(lanes / 256);
-    const uint64_t waves = lanes / 64;
-    uint64_t chunk = (nq + waves - 1) / waves;
-    uint64_t dyn_from = nq;
-    {
-        const uint64_t cs = (uint64_t)((double)nq * KX_DYN_STATIC) / waves;
-        if (cs >= (uint64_t)KX_DYN_CH && !std::getenv("OVS_NO_DYN")) {
-            chunk = cs;
-            dyn_from = cs * waves;
-            hipMemsetAsync(dyn, 0, sizeof *dyn, st);
-        } else {
-            dyn = nullptr;
-        }
-    }
     ovs_route_out* o = reinterpret_cast<ovs_route_out*>(out);   // or ovs_lookup_out (same size)
     XTrace T{};
     if (tr) { T.tarr = trace->tarr; T.cnode = trace->cnode; T.ctime = trace->ctime; T.ccap = trace->ccap; }
-#define KRL(ex, rg, xa)                                                                                                 \
-    do {                                                                                                                \
-        if (tr) hipLaunchKernelGGL((k_kad_refresh<ex, rg, xa, true>), dim3(blocks), dim3(256), 0, st, V, DC, C, X,    \
-                                   qkeys, qsrc, nq, chunk, dyn, dyn_from, o, sibs, responders, rtts, rpcs, err, T);                  \
-        else hipLaunchKernelGGL((k_kad_refresh<ex, rg, xa, false>), dim3(blocks), dim3(256), 0, st, V, DC, C, X,      \
-                                qkeys, qsrc, nq, chunk, dyn, dyn_from, o, sibs, responders, rtts, rpcs, err, T);                     \
-    } while (0)
-    if (a8) {
-        if (t.exact) { if (reg) KRL(true, true, 8); else KRL(true, false, 8); }
-        else { if (reg) KRL(false, true, 8); else KRL(false, false, 8); }
-    } else {
-        if (t.exact) { if (reg) KRL(true, true, 4); else KRL(true, false, 4); }
-        else if (def)
-            hipLaunchKernelGGL((k_kad_refresh<false, true, 3, false, true>), dim3(blocks), dim3(256), 0, st, V, DC, C, X,
-                               qkeys, qsrc, nq, chunk, dyn, dyn_from, o, sibs, responders, rtts, rpcs, err, T);
-        else { if (reg) KRL(false, true, 4); else KRL(false, false, 4); }
-    }
-#undef KRL
-    e = hipGetLastError();
+    std::unique_lock<std::mutex> lock(g_scratch_mu);
+    uint32_t* err = nullptr;
+    // the chosen instantiation: one lane per lookup, as many lanes as are resident at once (its
+    // occupancy-sized grid, capped by the batch, in whole blocks); the scratch is sized for the lanes
+    auto launch = [&](auto k) -> hipError_t {
+        using K = decltype(k);
+        uint64_t lanes = persist_waves<K::fn>(num_cu) * 64;
+        if (lanes > nq) lanes = nq;
+        lanes = (lanes + 255) / 256 * 256;
+        const uint64_t nhE = reg ? 0 : 2ull * R, resE = reg ? 0 : (uint64_t)(R > t.k ? R : t.k);
+        const uint64_t bytes = 8 + lanes * (nhE * (4 + 8 + 1) + resE * (4 + 8) + XMAXDEAD * 4) + 4;
+        if (g_scratch_cap[dev] < bytes) {
+            if (g_scratch[dev]) { hipDeviceSynchronize(); hipFree(g_scratch[dev]); }
+            g_scratch[dev] = nullptr; g_scratch_cap[dev] = 0;
+            const hipError_t me = hipMalloc(reinterpret_cast<void**>(&g_scratch[dev]), bytes);
+            if (me != hipSuccess) return me;
+            g_scratch_cap[dev] = bytes;
+        }
+        char* buf = g_scratch[dev];
+        XScratch X;
+        unsigned long long* dyn = reinterpret_cast<unsigned long long*>(buf);   // the dynamic tail's counter
+        char* p = buf + 8;
+        X.nh_d = reinterpret_cast<uint64_t*>(p); p += lanes * nhE * 8;
+        X.res_d = reinterpret_cast<uint64_t*>(p); p += lanes * resE * 8;
+        X.nh_idx = reinterpret_cast<uint32_t*>(p); p += lanes * nhE * 4;
+        X.res_idx = reinterpret_cast<uint32_t*>(p); p += lanes * resE * 4;
+        X.dead = reinterpret_cast<uint32_t*>(p); p += lanes * XMAXDEAD * 4;
+        err = reinterpret_cast<uint32_t*>(p); p += 4;
+        X.nh_used = reinterpret_cast<uint8_t*>(p);
+        X.lanes = lanes;
+        hipMemsetAsync(err, 0, 4, st);
+        // every wave of the lanes' grid is launched (the scratch is laid out for them)
+        const PersistPlan pl = persist_plan(nq, lanes / 64, dyn_tail, KX_TUNE, true);
+        if (pl.dyn) hipMemsetAsync(dyn, 0, sizeof *dyn, st);
+        hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, V, DC, C, X, qkeys, qsrc, nq, pl.chunk,
+                           pl.dyn ? dyn : nullptr, pl.dyn_from, o, sibs, responders, rtts, rpcs, err, T);
+        return hipGetLastError();
+    };
+    // exact compare and register form come as std::true_type / std::false_type; the slots and the
+    // trace are chosen here
+    auto pick = [&](auto ex, auto rg) -> hipError_t {
+        constexpr bool EX = decltype(ex)::value, RG = decltype(rg)::value;
+        if (a8) {
+            if (tr) return launch(PersistKernel<k_kad_refresh<EX, RG, 8, true>>{});
+            return launch(PersistKernel<k_kad_refresh<EX, RG, 8, false>>{});
+        }
+        if (tr) return launch(PersistKernel<k_kad_refresh<EX, RG, 4, true>>{});
+        return launch(PersistKernel<k_kad_refresh<EX, RG, 4, false>>{});
+    };
+    if (def) e = launch(PersistKernel<k_kad_refresh<false, true, 3, false, true>>{});
+    else if (t.exact) e = reg ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{});
+    else e = reg ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{});
+    if (!err) return e;      // no scratch: nothing was launched
     uint32_t herr = 0;
     hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st);
     const hipError_t e2 = hipStreamSynchronize(st);

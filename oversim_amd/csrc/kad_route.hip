@@ -21,10 +21,9 @@
 // single-GPU batch.
 #include "kad_dev.hpp"
 #include "kad_shard.hpp"
+#include "persist.hpp"
 
-#include <algorithm>
 #include <cstdio>
-#include <vector>
 
 #ifndef OVS_KAD_A
 #error "kad_route.hip is compiled with -DOVS_KAD_A=<alpha> -DOVS_KAD_EX=<0|1> (oversim_amd/build.py)"
@@ -47,20 +46,7 @@ namespace ovs {
 namespace {
 
 #ifdef OVS_KAD_TAIL
-// tail census (-DOVS_KAD_TAIL builds): each persistent wave's start and exit on the real-time
-// counter, read back and summarised by kad_launch (the spread of the waves' finishing times)
-constexpr int KAD_TAIL_MAX = 1 << 16;
-__device__ unsigned long long g_kad_tail[2 * KAD_TAIL_MAX];
-// lane 0 of the wave records the real-time counter in slot 2 * wave + which; the slot comes from
-// wave-uniform values, so nothing stays live across the kernel's loop (a first version that kept the
-// wave index and the start time live spilled the kernel)
-__device__ __forceinline__ void ovs_tail_mark(unsigned long long* arr, int max, int which)
-{
-    const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
-    const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wib;
-    const unsigned long long t = wall_clock64();
-    if (__lane_id() == 0 && w < (uint64_t)max) arr[2 * w + which] = t;
-}
+__device__ unsigned long long g_kad_tail[2 * PERSIST_TAIL_MAX];   // the tail census (persist.hpp)
 #endif
 
 struct SendNothing {
@@ -195,18 +181,14 @@ struct KadRouteIO {
     int me;
     int tl, bpb, full_ok;
     // dynamic tail (single-GPU batches, dyn != nullptr): static slices cover [0, dyn_from), the rest
-    // goes out KAD_DYN_CH lookups at a time from the zeroed counter *dyn (as K1's, chord.hip; K2's
-    // lookups run longer, so half K1's chunk: E 4.01 -> 3.97 ms against 64, profiles/r06_dyn/tune.txt)
+    // goes out KAD_TUNE.dyn_chunk lookups at a time from the zeroed counter *dyn (persist.hpp)
     unsigned long long* dyn;
     uint64_t dyn_from;
 };
 
-#ifndef KAD_DYN_CH
-#define KAD_DYN_CH 32
-#endif
-#ifndef KAD_DYN_STATIC
-#define KAD_DYN_STATIC 0.70
-#endif
+// K1's static share; K2's lookups run longer, so half K1's chunk: E 4.01 -> 3.97 ms against 64
+// (profiles/r06_dyn/tune.txt)
+constexpr PersistTune KAD_TUNE{0.70, 32};
 
 // SH: explicit tables with short sibling tables (KadTables::maybe_short): a send may have to count
 // the responder's scan (kad_response_size); snapshot tables never do
@@ -257,11 +239,7 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
     const int ns = LK ? LC.numSiblings : 1;
     uint32_t* st = static_cast<uint32_t*>(io.st);
 
-#ifndef OVS_NOCOOP
     __shared__ CoopLds lds;
-#else
-    CoopLds& lds = *(CoopLds*)nullptr;    // experiment build: never touched
-#endif
     bool active = false;
     bool dead = false;     // shard step: a listed lookup that does not run (source off the arc)
     bool go = false;       // migration step: a fresh lookup whose source lies off this arc moves at once
@@ -273,13 +251,10 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
         const uint64_t need = __ballot(!active);
         if (SM != 1 && more && need != 0 && cursor >= end) {
             // the static slice is spent: the next dynamic chunk (one atomic a chunk, lane 0)
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(io.dyn, (unsigned long long)KAD_DYN_CH);
-            const uint64_t nb = io.dyn_from + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                                               (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+            const uint64_t nb = persist_claim_chunk<KAD_TUNE.dyn_chunk>(io.dyn, io.dyn_from, lane);
             if (nb < nq) {
                 cursor = nb;
-                end = min(nb + (uint64_t)KAD_DYN_CH, nq);
+                end = min(nb + (uint64_t)KAD_TUNE.dyn_chunk, nq);
             } else {
                 more = false;
             }
@@ -302,12 +277,8 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
                     q = io.list[mine];
                     const uint8_t a = io.act[q];
                     dead = a == 0;
-#if !defined(OVS_SHARD_NOSUSPEND) && !defined(OVS_SHARD_NOLOAD)
                     if (a == 2) kad_lookup_init(L, io.qkeys[q], io.qsrc[q], V.xy);   // first visit
                     else if (a == 1) kad_state_get(L, st, io.sstride, q);
-#else
-                    if (a) kad_lookup_init(L, io.qkeys[q], io.qsrc[q], V.xy);   // cost experiment (W = 1 only)
-#endif
                 } else {
                     q = mine;
                     kad_lookup_init(L, io.qkeys[q], io.qsrc[q], V.xy);
@@ -330,9 +301,7 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
             // pending) leaves the lane idle through the findNode, merge and send phases: the lane
             // takes its next event in the same iteration instead (at most A pending events).  With
             // α = 3 these are ~40 % of the events (most parallel responses arrive a step late).
-#ifndef OVS_KAD_ONE_EVENT
             for (int r = 0; r < A; ++r) {
-#endif
                 if (SHARD) {
                     const RemoteReady<C> rd{static_cast<const KadResN<C>*>(io.res), q * A, V.lo, V.hi};
                     ph = kad_event_begin<A, EX, LK>(L, V, DC, LC, rd, rec, ev);
@@ -341,10 +310,8 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
                 } else {
                     ph = kad_event_begin<A, EX, LK>(L, V, DC, LC, AlwaysReady{}, rec, ev);
                 }
-#ifndef OVS_KAD_ONE_EVENT
                 if (ph != KEV_HANDLED || kad_lookup_done(L)) break;
             }
-#endif
             const bool local = !SM || (ev.r >= V.lo && ev.r < V.hi);
             // migration step: a call sent from another rank names no row of this one (MigSend:
             // NONE); its responder's row here is the responder's own line's
@@ -370,18 +337,11 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
         // instantiation (networks with IDs sharing their top 63 bits) keeps the per-lane scan: its
         // tie fallbacks in the cooperative merge made the register allocator emit misaligned
         // 96-bit spills that gfx950 rejects.
-#ifndef OVS_NOCOOP
         if constexpr (!EX && C == 8) {
             kad_coop_sibzone<EX>(V, coop, ev.r, ev.geo, ev.boff, ev.pre, L.K, lds);
-#ifdef OVS_DUP_COOP
-            kad_coop_sibzone<EX>(V, coop, ev.r, ev.geo, ev.boff, ev.pre, L.K, lds);   // cost experiment
-#endif
         } else {
             coop = false;
         }
-#else
-        coop = false;
-#endif
 
         // phase 3 (per lane): the rest of the findNode, the LookupVector, the sends
         if (SHARD && dead) {
@@ -425,18 +385,6 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
                     const RespGeo g = ev.rg();
                     n = kad_find_node_blk<EX, C>(V, ev.r, g, L.K, ev.numR, ev.sb(), fb, ns,
                                                  g.m <= g.endIndex ? rb_pre(ev.pre) : -1, rb_r0(ev.pre));
-#ifdef OVS_DUP_LANEFIND
-                    {   // cost experiment: the per-lane findNode again
-                        K160 K2 = L.K;
-                        asm volatile("" : "+v"(K2.w[0]));
-                        BlkN<C> b2;
-                        const int n2 = kad_find_node_blk<EX, C>(V, ev.r, g, K2, ev.numR, ev.sb(), b2, ns,
-                                                                g.m <= g.endIndex ? rb_pre(ev.pre) : -1, rb_r0(ev.pre));
-                        uint32_t z = (uint32_t)n2;
-                        for (int k = 0; k < C; ++k) z ^= b2.x[k] ^ (uint32_t)b2.d[k] ^ (uint32_t)(b2.d[k] >> 32);
-                        asm volatile("" :: "v"(z));
-                    }
-#endif
                 }
 #pragma unroll
                 for (int k = 0; k < C; ++k) { res.idx[k] = fb.x[k]; res.d[k] = fb.d[k]; }
@@ -523,9 +471,7 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
                 active = false;
             } else if (SHARD && ph == KEV_WAIT) {
                 // the earliest event waits for an owner's answer: suspended until the next round
-#if !defined(OVS_SHARD_NOSUSPEND) && !defined(OVS_SHARD_NOSTORE)
                 kad_state_put(st, io.sstride, q, L);
-#endif
                 io.act[q] = 1;
                 io.ltag[q] = 1;
                 active = false;
@@ -533,7 +479,7 @@ __global__ __launch_bounds__(256, ((SM && (EX || LK)) || C > 8 || (SM == 2 && (O
         }
     }
 #ifdef OVS_KAD_TAIL
-    ovs_tail_mark(g_kad_tail, KAD_TAIL_MAX, 1);
+    ovs_tail_mark(g_kad_tail, PERSIST_TAIL_MAX, 1);
 #endif
 }
 
@@ -544,35 +490,13 @@ template <int A, bool RECORD, bool EX, bool LK, int SM, int C = 8, bool SH = tru
 static hipError_t kad_launch(const KadView& V, const DelayConsts& DC, const KadLC& LC, KadRouteIO io, int num_cu,
                              hipStream_t st)
 {
-    // occupancy of this instantiation (the same on every gfx950 device; a function-local static is
-    // initialised once, thread-safely)
-    static const int bpc = [] {
-        int b = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_kad_route<A, RECORD, EX, LK, SM, C, SH, DEF>, 256, 0) !=
-                hipSuccess ||
-            b < 1)
-            b = 1;
-        return b;
-    }();
-#ifndef OVS_KAD_OVERSUB
-#define OVS_KAD_OVERSUB 1
-#endif
-    // OVS_KAD_OVERSUB > 1 (A/B builds): that many waves per resident slot, each with a shorter slice
-    const uint64_t waves = (uint64_t)num_cu * (uint64_t)bpc * 4 * (SM ? 1 : OVS_KAD_OVERSUB);
-    io.chunk = (io.nq + waves - 1) / waves;
-    if (io.chunk < 1) io.chunk = 1;
-    const uint64_t need_waves = (io.nq + io.chunk - 1) / io.chunk;
-    const uint64_t blocks = (need_waves + 3) / 4;
-    if (SM != 1 && io.dyn) {
-        // static slices cover KAD_DYN_STATIC of the batch, the rest goes out in chunks (small batches: static)
-        const uint64_t cs = (uint64_t)((double)io.nq * KAD_DYN_STATIC) / (blocks * 4);
-        if (cs < (uint64_t)KAD_DYN_CH) {
-            io.dyn = nullptr;
-        } else {
-            io.chunk = cs;
-            io.dyn_from = cs * blocks * 4;
-        }
-    }
+    // (the request/response shard step, SM = 1, sizes its slices on the device: static only)
+    const PersistPlan pl = persist_plan(io.nq, persist_waves<k_kad_route<A, RECORD, EX, LK, SM, C, SH, DEF>>(num_cu),
+                                        SM != 1 && io.dyn != nullptr, KAD_TUNE);
+    const uint64_t blocks = pl.blocks;
+    io.chunk = pl.chunk;
+    io.dyn_from = pl.dyn_from;
+    if (!pl.dyn) io.dyn = nullptr;
 #ifdef OVS_KAD_STATS
     unsigned long long z[8] = {};
     hipMemcpyToSymbolAsync(HIP_SYMBOL(g_kad_stats), z, sizeof z, 0, hipMemcpyHostToDevice, st);
@@ -580,22 +504,7 @@ static hipError_t kad_launch(const KadView& V, const DelayConsts& DC, const KadL
     hipLaunchKernelGGL((k_kad_route<A, RECORD, EX, LK, SM, C, SH, DEF>), dim3((unsigned)blocks), dim3(256), 0, st, V, DC, LC,
                        io);
 #ifdef OVS_KAD_TAIL
-    if (!SM) {
-        const uint64_t nw = blocks * 4 < (uint64_t)KAD_TAIL_MAX ? blocks * 4 : (uint64_t)KAD_TAIL_MAX;
-        std::vector<unsigned long long> tt(2 * nw);
-        hipMemcpyFromSymbolAsync(tt.data(), HIP_SYMBOL(g_kad_tail), sizeof(unsigned long long) * 2 * nw, 0,
-                                 hipMemcpyDeviceToHost, st);
-        hipStreamSynchronize(st);
-        unsigned long long t0 = ~0ull;
-        std::vector<double> fin;
-        for (uint64_t w = 0; w < nw; ++w) t0 = tt[2 * w + 1] < t0 ? tt[2 * w + 1] : t0;
-        for (uint64_t w = 0; w < nw; ++w) fin.push_back((double)(tt[2 * w + 1] - t0) * 0.01);   // 100 MHz -> us
-        std::sort(fin.begin(), fin.end());
-        auto pct = [&](double f) { return fin[(size_t)(f * (fin.size() - 1))]; };
-        fprintf(stderr, "kadtail waves=%llu chunk=%llu finish_us_after_first_exit p0=%.1f p10=%.1f p50=%.1f p90=%.1f p99=%.1f max=%.1f\n",
-                (unsigned long long)nw, (unsigned long long)io.chunk, pct(0), pct(0.1), pct(0.5), pct(0.9), pct(0.99),
-                fin.back());
-    }
+    if (!SM) persist_tail_report("kadtail", HIP_SYMBOL(g_kad_tail), blocks * 4, io.chunk, st);
 #endif
 #ifdef OVS_KAD_STATS
     hipMemcpyFromSymbolAsync(z, HIP_SYMBOL(g_kad_stats), sizeof z, 0, hipMemcpyDeviceToHost, st);
@@ -628,9 +537,7 @@ hipError_t kad_route_launch(const KadView& V, const DelayConsts& DC, const KadLC
     }
     if (sibs) return kad_launch<A, false, EX, true, 0, 8, false>(V, DC, LC, io, num_cu, st);
     if (hopseq) return kad_launch<A, true, EX, false, 0, 8, false>(V, DC, LC, io, num_cu, st);
-#ifndef OVS_KAD_NO_DEF
     if (kad_is_def_lc(LC)) return kad_launch<A, false, EX, false, 0, 8, false, true>(V, DC, LC, io, num_cu, st);
-#endif
     return kad_launch<A, false, EX, false, 0, 8, false>(V, DC, LC, io, num_cu, st);
 }
 

@@ -11,6 +11,7 @@
 // loops (walkSuccessorList 572-582, walkDeBruijnList 558-570).  Finished lanes refill from the
 // wave's slice of the batch (ballot + popcount); the grid is persistent.
 #include "koorde.hpp"
+#include "persist.hpp"
 
 #include <cstdlib>
 
@@ -436,18 +437,13 @@ constexpr int KVL = 16;
 // DEF: the default configuration (default.ini: successorListSize 16, shiftingBits 4, useOtherLookup
 // and useSucList on, hopCountMax 50) as compile-time constants -- the start-key arithmetic's
 // modulo by shiftingBits folds to a mask: 5963 -> 4931 static instructions
-// the dynamic tail (as K1's, chord.hip): static slices cover [0, from), the rest goes out
-// K3_DYN_CH lookups at a time from the zeroed per-launch counter *ctr (nullptr: static slices only)
+// the dynamic tail (persist.hpp; K1's share and chunk): static slices cover [0, from), the rest goes out
+// K3_TUNE.dyn_chunk lookups at a time from the zeroed per-launch counter *ctr (nullptr: static slices only)
 struct KDyn {
     unsigned long long* ctr;
     uint64_t from;
 };
-#ifndef K3_DYN_CH
-#define K3_DYN_CH 64
-#endif
-#ifndef K3_DYN_STATIC
-#define K3_DYN_STATIC 0.70
-#endif
+constexpr PersistTune K3_TUNE{0.70, 64};
 
 template <bool KR, bool RECORD, bool DEF = false>
 __global__ __launch_bounds__(256, KR ? OVS_KOORDE_WAVES : 1) void k_koorde_route(KView V0, const double2* __restrict__ xy, DelayConsts DC, int hcm0,
@@ -483,13 +479,10 @@ __global__ __launch_bounds__(256, KR ? OVS_KOORDE_WAVES : 1) void k_koorde_route
     while (true) {
         const uint64_t need = __ballot(!active);
         if (more && need != 0 && cursor >= end) {
-            unsigned long long b = 0;
-            if (lane == 0) b = atomicAdd(dy.ctr, (unsigned long long)K3_DYN_CH);
-            const uint64_t nb = dy.from + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
-                                           (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+            const uint64_t nb = persist_claim_chunk<K3_TUNE.dyn_chunk>(dy.ctr, dy.from, lane);
             if (nb < nq) {
                 cursor = nb;
-                end = min(nb + (uint64_t)K3_DYN_CH, nq);
+                end = min(nb + (uint64_t)K3_TUNE.dyn_chunk, nq);
             } else {
                 more = false;
             }
@@ -656,12 +649,7 @@ hipError_t koorde_build(const KeyRec* recs, const double2* xy, uint32_t n, int s
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // the record form covers successor / de Bruijn lists of up to 16 nodes (the Koorde defaults)
-#ifdef OVS_KOORDE_NOREC
-    const bool rec_form = false;      // diagnostic build: the list form only
-#else
-    const bool rec_form = true;
-#endif
-    if (rec_form && t.ns <= KREC_LIST && deBruijnListSize <= KREC_LIST) {
+    if (t.ns <= KREC_LIST && deBruijnListSize <= KREC_LIST) {
         e = hipMalloc(&t.rec, sizeof(KoordeRec) * n);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_koorde_rec, dim3(nblk(n, 256)), dim3(256), 0, st, recs, xy, t.nd, n, t.rec);
@@ -676,64 +664,22 @@ hipError_t koorde_route(const KoordeTables& t, const KeyRec* recs, const double2
                         uint32_t* hopseq, bool record, uint32_t* rpcs, int num_cu, hipStream_t st,
                         unsigned long long* dyn)
 {
-    // a grid of `waves` persistent waves: static slices, with the dynamic tail when dyn is given
-    auto slices = [&](uint64_t waves, uint64_t* chunk, uint64_t* blocks, KDyn* dy) {
-        uint64_t c = (nq + waves - 1) / waves;
-        if (c < 1) c = 1;
-        *blocks = ((nq + c - 1) / c + 3) / 4;
-        dy->ctr = nullptr;
-        dy->from = nq;
-        const uint64_t cs = dyn ? (uint64_t)((double)nq * K3_DYN_STATIC) / (*blocks * 4) : 0;
-        if (cs >= (uint64_t)K3_DYN_CH) {
-            c = cs;
-            dy->ctr = dyn;
-            dy->from = cs * *blocks * 4;
-        }
-        *chunk = c;
-    };
     if (nq == 0) return hipSuccess;
     if (!hopseq) return hipErrorInvalidValue;
-    static int bpc[4] = {0, 0, 0, 0};
-    const int kr = t.rec ? 1 : 0;
-    const int ki = kr + (record ? 2 : 0);
-#define KRT(a, b) k_koorde_route<a, b>
-    if (bpc[ki] == 0) {
-        int b = 0;
-        const hipError_t oe =
-            kr ? (record ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, KRT(true, true), 256, 0)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, KRT(true, false), 256, 0))
-               : (record ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, KRT(false, true), 256, 0)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, KRT(false, false), 256, 0));
-        bpc[ki] = (oe == hipSuccess && b > 0) ? b : 1;
-    }
-    const uint64_t waves = (uint64_t)num_cu * (uint64_t)bpc[ki] * 4;
-    uint64_t chunk = 0, blocks = 0;
-    KDyn dy;
-    slices(waves, &chunk, &blocks, &dy);
-#define KRL(a, b) hipLaunchKernelGGL((KRT(a, b)), dim3((unsigned)blocks), dim3(256), 0, st, make_view(t, recs), xy, DC, \
-                                     hopCountMax, keys, src, nq, chunk, dy, out, hopseq, rpcs)
     const KView kv = make_view(t, recs);
-#ifdef OVS_KOORDE_NO_DEF
-    const bool def = false;             // A/B build: the generic instantiation
-#else
+    // the chosen instantiation's occupancy-sized grid: static slices, with the dynamic tail when dyn is given
+    auto launch = [&](auto k) {
+        using K = decltype(k);
+        const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, K3_TUNE);
+        const KDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+        hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, kv, xy, DC, hopCountMax, keys, src, nq,
+                           pl.chunk, dy, out, hopseq, rpcs);
+    };
+    const bool kr = t.rec != nullptr;
     const bool def = kr && !record && kv.ns == 16 && kv.sb == 4 && kv.useOther == 1 && kv.useSuc == 1 && hopCountMax == 50;
-#endif
-    if (def) {
-        static int bpd = 0;
-        if (bpd == 0) {
-            int b = 0;
-            bpd = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_koorde_route<true, false, true>, 256, 0) == hipSuccess && b > 0) ? b : 1;
-        }
-        const uint64_t wd = (uint64_t)num_cu * (uint64_t)bpd * 4;
-        uint64_t cd = 0, bd = 0;
-        KDyn dd;
-        slices(wd, &cd, &bd, &dd);
-        hipLaunchKernelGGL((k_koorde_route<true, false, true>), dim3((unsigned)bd), dim3(256), 0, st, kv, xy, DC, hopCountMax, keys,
-                           src, nq, cd, dd, out, hopseq, rpcs);
-    } else if (kr) { if (record) KRL(true, true); else KRL(true, false); }
-    else { if (record) KRL(false, true); else KRL(false, false); }
-#undef KRL
-#undef KRT
+    if (def) launch(PersistKernel<k_koorde_route<true, false, true>>{});
+    else if (kr) { if (record) launch(PersistKernel<k_koorde_route<true, true>>{}); else launch(PersistKernel<k_koorde_route<true, false>>{}); }
+    else { if (record) launch(PersistKernel<k_koorde_route<false, true>>{}); else launch(PersistKernel<k_koorde_route<false, false>>{}); }
     return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 #include "kad_shard.hpp"
 #include "koorde.hpp"
 #include "launch.hpp"
+#include "persist.hpp"
 #include "stats.hpp"
 
 using namespace ovs;
@@ -190,7 +191,7 @@ void free_kad_shard(ovs_ctx* c)
 // nullptr when none can be had -- the kernel then runs static slices only.
 DynSlots::Lease dyn_acquire(ovs_ctx* c, uint64_t n, hipStream_t s)
 {
-    if (std::getenv("OVS_NO_DYN")) return {};             // A/B: static slices only
+    if (!persist_dyn_enabled()) return {};                // A/B: static slices only
     if (n < (1ull << 18)) return {};                      // small batches: static slices (no memset, no event)
     return c->dyn.acquire(s);
 }
@@ -1575,7 +1576,7 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
         bool cap_err = false;
         // dhop was filled with NONE above: the kernel leaves the rows unpadded
         e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), c->P.lookupRedundantNodes, 1, true,
-                           dk, ds, n, dout, dres, dhop, nullptr, drpc, c->num_cu, s, &cap_err, nullptr, false,
+                           dk, ds, n, dout, dres, dhop, nullptr, drpc, c->num_cu, s, persist_dyn_enabled(), &cap_err, nullptr, false,
                            hop_seq == nullptr /* nobody reads the visited sets: their first entries in LDS */);
         if (e == hipSuccess && cap_err) return fail(c, OVS_ENOTSUP, "a lookup exceeded the kernel's capacity (64 timed-out nodes)");
     } else if (c->P.routingType == 1 || c->P.routingType == 2 || kad_src) {
@@ -1697,7 +1698,7 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
         // lookupRpc with EXHAUSTIVE_ITERATIVE_ROUTING: redundantNodes = lookupRedundantNodes, numSiblings = ns
         bool cap_err = false;
         e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, P, delay_consts(P), P.lookupRedundantNodes, ns, false, dk, ds,
-                           n, dout, dsib, dhop, nullptr, nullptr, c->num_cu, s, &cap_err, nullptr, false,
+                           n, dout, dsib, dhop, nullptr, nullptr, c->num_cu, s, persist_dyn_enabled(), &cap_err, nullptr, false,
                            true /* a LookupCall records no hop sequence: the visited sets' first entries in LDS */);
         if (e == hipSuccess && cap_err) e = hipErrorNotSupported;
     } else if (kad_rec) {
@@ -1765,7 +1766,7 @@ ovs_status ovs_kad_refresh_batch(ovs_ctx* c, const ovs_key160* keys, const uint3
     }
     bool cap_err = false;
     const hipError_t e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, P, delay_consts(P), R, R, false, dk, ds, n, dout,
-                                        dsib, dresp, drtt, drpc, c->num_cu, s, &cap_err, nullptr,
+                                        dsib, dresp, drtt, drpc, c->num_cu, s, persist_dyn_enabled(), &cap_err, nullptr,
                                         responders != nullptr /* else the internal visited lists: no padding */,
                                         responders == nullptr /* ... and their first entries in LDS */);
     vis.release();
@@ -1902,7 +1903,7 @@ ovs_status ovs_kad_maintenance_round(ovs_ctx* c, const uint32_t* nodes, uint64_t
         const KadExhTrace tr{dta, dcn, dct, ccap};
         bool cap_err = false;
         const hipError_t e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, P, DC, Rg, Rg, false, dk, ds, ng, dout, dsib,
-                                            dresp, nullptr, drpc, c->num_cu, s, &cap_err, &tr);
+                                            dresp, nullptr, drpc, c->num_cu, s, persist_dyn_enabled(), &cap_err, &tr);
         if (e != hipSuccess) return hip_fail(c, e, "maintenance round: refresh lookups");
         if (cap_err) return fail(c, OVS_ENOTSUP, "a refresh lookup exceeded the kernel's capacity");
         if (F.finish() != hipSuccess) return frame_fail(c, F);

@@ -1,0 +1,151 @@
+// persist.hpp -- the persistent-slice scheduler shared by the lane-refill route kernels: K1
+// (k_chord_lanes, chord.hip), K2 (k_kad_route, kad_route.hip), K2x (k_kad_refresh, kad_refresh.hip)
+// and K3 (k_koorde_route, koorde.hip).
+//
+// Each launches an occupancy-sized persistent grid and gives every wave one contiguous static slice
+// of the batch; a lane whose lookup ended takes the wave's next one by ballot + popcount (the
+// kernel's own refill body).  Persistent waves finish their static slices up to a quarter of the
+// kernel apart (the tail census below), so with a zeroed per-launch counter the static slices cover
+// only a share of the batch and the rest goes out in chunks of a few lookups, one atomic a chunk:
+// the waves that run ahead take more (the dynamic tail).  The share and the chunk are per-kernel
+// tunables (PersistTune), kept next to their kernels.
+//
+// The plan (persist_plan) is plain C++: it compiles without a HIP compiler
+// (tests/persist_plan_driver.cpp).  The occupancy query and the tail census need one (__HIPCC__).
+// On the device the claim of the next dynamic chunk is persist_claim_chunk; a wave's cursor / end /
+// more stay locals of each kernel's refill: as members of a shared slice object they compiled to
+// different register allocations (K1's shard step +18 spilled SGPRs, K2 and K2x a few spilled
+// VGPRs more or fewer), and these kernels sit at their occupancy limits.
+#pragma once
+
+#include <cstdint>
+#include <cstdlib>
+
+namespace ovs {
+
+// OVS_NO_DYN=1 (A/B and the dynamic-tail tests): static slices only.  Read per call, here only:
+// the callers pass the decision down (no counter / dyn_tail = false)
+inline bool persist_dyn_enabled() { return std::getenv("OVS_NO_DYN") == nullptr; }
+
+struct PersistTune {
+    double static_share;   // the share of a batch the static slices cover when the tail is on
+    uint32_t dyn_chunk;    // lookups per dynamic chunk
+};
+
+struct PersistPlan {
+    uint64_t chunk;        // lookups of each wave's static slice: wave w owns [w * chunk, (w + 1) * chunk)
+    uint64_t blocks;       // 256-thread blocks (4 waves) to launch
+    uint64_t dyn_from;     // the static slices end here (cut at n); [dyn_from, n) goes out in chunks
+    bool dyn;              // the dynamic tail is on (dyn_from < n, the counter is used)
+};
+
+// n > 0 lookups over `waves` resident waves (blocks per CU x CUs x 4).  Static: slices of
+// ceil(n / waves), and only the blocks whose waves have one are launched; whole_grid (K2x, whose grid
+// is its lane-capped scratch: waves = lanes / 64, a multiple of 4) launches every wave.  With a
+// counter the static slices shrink to static_share of the batch, unless a slice would then be shorter
+// than one dynamic chunk (small batches stay static).
+inline PersistPlan persist_plan(uint64_t n, uint64_t waves, bool counter, PersistTune t, bool whole_grid = false)
+{
+    PersistPlan p{};
+    p.chunk = (n + waves - 1) / waves;
+    if (p.chunk < 1) p.chunk = 1;
+    const uint64_t used = whole_grid ? waves : (n + p.chunk - 1) / p.chunk;
+    p.blocks = (used + 3) / 4;
+    p.dyn_from = n;
+    const uint64_t grid = p.blocks * 4;
+    const uint64_t cs = (uint64_t)((double)n * t.static_share) / grid;
+    if (counter && cs >= (uint64_t)t.dyn_chunk) {
+        p.chunk = cs;
+        p.dyn_from = cs * grid;
+        p.dyn = true;
+    }
+    return p;
+}
+
+}  // namespace ovs
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <vector>
+
+namespace ovs {
+
+// A kernel instantiation as a type, so that a launch ladder chooses it once (a generic lambda takes
+// PersistKernel<k<...>>{} and has the kernel as the constant K::fn for the occupancy and the launch)
+template <auto Kernel>
+struct PersistKernel {
+    static constexpr auto fn = Kernel;
+};
+
+// resident 256-thread blocks per CU of a kernel instantiation (the same on every gfx950 device; a
+// function-local static is initialised once, thread-safely)
+template <auto Kernel>
+int persist_blocks_per_cu()
+{
+    static const int bpc = [] {
+        int b = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, Kernel, 256, 0) != hipSuccess || b < 1) b = 1;
+        return b;
+    }();
+    return bpc;
+}
+
+// the resident waves of a kernel instantiation's occupancy-sized grid (4 waves per block)
+template <auto Kernel>
+uint64_t persist_waves(int num_cu)
+{
+    return (uint64_t)num_cu * (uint64_t)persist_blocks_per_cu<Kernel>() * 4;
+}
+
+// The claim of a wave's next dynamic chunk: lane 0 adds CH to the launch's counter (one atomic a
+// chunk), and the chunk's first lookup, dyn_from + the counter's old value, comes back wave-uniform.
+// The caller, a wave whose slice is spent, takes [nb, min(nb + CH, n)) when nb < n; otherwise the
+// batch is handed out.  It returns a value only: cursor / end / more stay the kernel's own locals,
+// so nothing new is live across the kernel's loop
+template <uint32_t CH>
+__device__ __forceinline__ uint64_t persist_claim_chunk(unsigned long long* ctr, uint64_t dyn_from, int lane)
+{
+    unsigned long long b = 0;
+    if (lane == 0) b = atomicAdd(ctr, (unsigned long long)CH);
+    return dyn_from + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
+                       (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
+}
+
+// tail census (-DOVS_K1_TAIL / -DOVS_KAD_TAIL builds): each persistent wave's exit on the 100 MHz
+// real-time clock, so the spread of the waves' finishing times (the kernel's tail) can be read off
+// one launch
+constexpr int PERSIST_TAIL_MAX = 1 << 16;
+// lane 0 of the wave records the real-time counter in slot 2 * wave + which; the slot comes from
+// wave-uniform values, so nothing stays live across the kernel's loop (a first version that kept the
+// wave index and the start time live spilled the kernel)
+__device__ __forceinline__ void ovs_tail_mark(unsigned long long* arr, int max, int which)
+{
+    const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
+    const uint64_t w = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wib;
+    const unsigned long long t = wall_clock64();
+    if (__lane_id() == 0 && w < (uint64_t)max) arr[2 * w + which] = t;
+}
+// the census array `sym` (a __device__ array of 2 * PERSIST_TAIL_MAX) read back after the launch on
+// s: the waves' exit times as percentiles after the first exit
+inline void persist_tail_report(const char* tag, const void* sym, uint64_t waves, uint64_t chunk, hipStream_t s)
+{
+    const uint64_t nw = waves < (uint64_t)PERSIST_TAIL_MAX ? waves : (uint64_t)PERSIST_TAIL_MAX;
+    std::vector<unsigned long long> tt(2 * nw);
+    hipMemcpyFromSymbolAsync(tt.data(), sym, sizeof(unsigned long long) * 2 * nw, 0, hipMemcpyDeviceToHost, s);
+    hipStreamSynchronize(s);
+    unsigned long long t0 = ~0ull;
+    std::vector<double> fin;
+    for (uint64_t w = 0; w < nw; ++w) t0 = tt[2 * w + 1] < t0 ? tt[2 * w + 1] : t0;
+    for (uint64_t w = 0; w < nw; ++w) fin.push_back((double)(tt[2 * w + 1] - t0) * 0.01);   // 100 MHz -> us
+    std::sort(fin.begin(), fin.end());
+    auto pct = [&](double f) { return fin[(size_t)(f * (fin.size() - 1))]; };
+    fprintf(stderr, "%s waves=%llu chunk=%llu finish_us_after_first_exit p0=%.1f p10=%.1f p50=%.1f p90=%.1f p99=%.1f max=%.1f\n",
+            tag, (unsigned long long)nw, (unsigned long long)chunk, pct(0), pct(0.1), pct(0.5), pct(0.9), pct(0.99),
+            fin.back());
+}
+
+}  // namespace ovs
+#endif

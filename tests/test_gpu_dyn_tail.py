@@ -51,3 +51,59 @@ def test_concurrent_streams_share_no_counter(engine: KbrEngine, overlay, monkeyp
     torch.cuda.synchronize()
     for i, (b, o) in enumerate(outs):
         assert np.array_equal(o.cpu().numpy(), ref[b]), f"launch {i} (batch {b}) differs from the static route"
+
+
+# 3 * 2^18 + 37 lookups: at most 8 blocks of 4 waves fit on a CU, so with 256 CUs a static slice of
+# 0.70 * n / (256 * 8 * 4) = 67 lookups holds K1's and K3's 64-lookup chunk (and K2's 32) whatever the
+# kernels' occupancy -- the tail is on -- and the dynamic region is no multiple of the chunk: the last
+# chunk handed out is partial
+N_PARTIAL = 3 * (1 << 18) + 37
+
+
+def _static_and_dynamic(monkeypatch, run):
+    """run() once with static slices only and once with the dynamic tail."""
+    monkeypatch.setenv("OVS_NO_DYN", "1")
+    ref = run()
+    monkeypatch.delenv("OVS_NO_DYN")
+    return ref, run()
+
+
+def _assert_same(ref: dict, got: dict):
+    assert ref.keys() == got.keys()
+    for f in ref:
+        assert np.array_equal(ref[f], got[f]), f"{f} differs from the static run"
+
+
+@pytest.mark.parametrize("overlay", ["chord", "kademlia"])
+def test_tail_with_partial_last_chunk_equals_static(engine: KbrEngine, overlay, monkeypatch):
+    net = W.population(1 << 16, 91)
+    if overlay == "chord":
+        engine.set_params(Params.chord())
+        engine.chord_load(net.ids, net.xy)
+    else:
+        engine.set_params(Params.kademlia().replace(lookupParallelRpcs=3))
+        engine.kad_load(net.ids, net.xy)
+    keys, src = W.lookups(net.ids, N_PARTIAL, 104, node_ids=False)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.lookup(keys, src))
+    _assert_same(ref, got)
+
+
+def test_koorde_tail_equals_static(engine: KbrEngine, monkeypatch):
+    net = W.population(1 << 12, 92)
+    engine.set_params(Params.koorde())
+    engine.koorde_load(net.ids, net.xy)
+    keys, src = W.lookups(net.ids, N_PARTIAL, 105, node_ids=False)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.lookup(keys, src))
+    _assert_same(ref, got)
+
+
+def test_refresh_tail_equals_static(engine: KbrEngine, monkeypatch):
+    """K2x (ovs_kad_refresh_batch): 4101 lookups fill 17 blocks = 68 waves, whose static slices of
+    0.40 * 4101 / 68 = 24 lookups hold a 16-lookup chunk: the tail is on, its last chunk partial
+    (4101 - 24 * 68 = 2469 = 154 * 16 + 5)."""
+    net = W.population(1 << 12, 93)
+    engine.set_params(Params.kademlia().replace(lookupParallelRpcs=3))
+    engine.kad_load(net.ids, net.xy)
+    keys, src = W.lookups(net.ids, 4101, 106, node_ids=False)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.kad_refresh(keys, src, 8))
+    _assert_same(ref, got)

@@ -78,3 +78,21 @@ def test_call_frame_clean_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_persist_plan_clean_under_asan_ubsan(tmp_path):
+    """The persistent-slice scheduler's host plan (oversim_amd/csrc/persist.hpp: static slices, block
+    count and dynamic split of K1, K2, K2x and K3) built with plain g++ under ASan/UBSan -Werror: the
+    slices and the dynamic region partition every batch, a replay of waves claiming chunks in an
+    arbitrary interleaving visits every index once, and each kernel's numbers equal literal values
+    worked out from its former launcher's formulas (tests/persist_plan_driver.cpp).  No HIP compiler
+    and no HIP library."""
+    exe = tmp_path / "persist_plan_driver"
+    c = ["g++", "-std=c++17", *SAN, *WARN, "-I", str(ROOT / "oversim_amd" / "csrc"),
+         str(ROOT / "tests" / "persist_plan_driver.cpp"), "-o", str(exe)]
+    r = subprocess.run(c, capture_output=True, text=True)
+    assert r.returncode == 0, f"{' '.join(c)}\n{r.stdout}{r.stderr}"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
