@@ -480,6 +480,14 @@ __device__ __forceinline__ int cmp_gap(const ChordView& V, const K160& D, uint64
     return k_lt(D, G) ? -1 : (k_eq(D, G) ? 0 : 1);
 }
 
+// top64(a - b) without the low words of the difference: the top 64 bits' difference less the borrow
+// of the low 96 bits
+__device__ __forceinline__ uint64_t top64_sub(const K160& a, const K160& b)
+{
+    const bool borrow = (a.w[2] < b.w[2]) | ((a.w[2] == b.w[2]) & (lo64(a) < lo64(b)));
+    return top64(a) - top64(b) - (borrow ? 1u : 0u);
+}
+
 struct LaneIO {
     // single-GPU route (ovs_route_batch)
     const K160* __restrict__ qkeys;
@@ -528,7 +536,8 @@ __device__ unsigned long long g_k1_stats[8];
 #endif
 
 // LKC: a LookupCall batch (ovs_lookup_batch): the responsible node's larger answer, no route message
-// minimum waves per SIMD: every instantiation at the single-GPU route's 5 (its 89 VGPRs); the shard
+// minimum waves per SIMD: every instantiation at the single-GPU route's 5 (its 95 VGPRs of the 96
+// that allocation leaves: a new loop-carried value has to pay for its registers); the shard
 // step's outcome staging had taken it to 98 VGPRs = 4 waves/SIMD
 #ifndef OVS_K1_WAVES
 #define OVS_K1_WAVES 5
@@ -570,6 +579,10 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
     K160 C;
     uint32_t row = 0;
     uint64_t gSL = 0;
+    // top64(K - C), kept from the arrival at C: PROBE and WIN decide on it, on the exact keys only on a
+    // tie.  (The shard step re-derives it there, and the finish's coordinate delay too: at its 96
+    // VGPRs the two more live registers spill)
+    uint64_t Dt = 0;
     int pi = 0, ilo = 0, esl = 0;
     uint32_t fb = 0;                  // closestPreceedingNode's successor fallback (Chord.cc:653-658)
     bool gTx = false;                 // temp == K (node-ID key): a finger hits only when it is K
@@ -742,6 +755,11 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
             uint32_t nxt = NONE;      // next hop chosen this iteration ...
             bool nxt_node = false;    // ... whose header must be read from its NodeRec
             bool nxt_sib = false;
+            // iterative: the coordinate delay S <-> cur of the response that arrived this iteration.
+            // A lookup that finishes at a responder other than its source finishes in the iteration
+            // that responder answered, so its route message S -> R reuses this value (one coord_ns per
+            // iteration instead of two)
+            int64_t cd = 0;
             lp = nullptr;
             // an off-arc responder whose decision needs its owner's rows (a finger below the
             // replicated levels, or its successor window): the lookup goes to the owner as a
@@ -793,9 +811,7 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                 A.gSL = u64(L3.x, L3.y);
                 if (ph == PH_START) {
                     A.row = L1.y;
-                    // isSiblingFor(cur, K, 1): K in (pred, cur]  <=>  D == 0 or D > pred - cur (Chord.cc:452-457)
-                    const K160 D = k_sub(K, A.k);
-                    asib = k_zero(D) || cmp_gap(V, D, u64(L3.z, L3.w), A.k, cur == 0 ? V.n - 1 : cur - 1) > 0;
+                    // (isSiblingFor(cur, K, 1) is decided below, with the D = K - cur every arrival needs)
                     // the source's own line (a lookup that left its source never comes back to START
                     // in one launch; a shard record's START is its responder's: coordinates from FETCH)
                     if (!REC && (!SHARD || local)) { sx = A.x; sy = A.y; }
@@ -806,19 +822,30 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                     if (REC && pend) t += DC.msgRoute + coord_ns(sx, sy, A.x, A.y, DC.round);   // to a successor
                     arrived = true;
                 } else if (ph == PH_PROBE) {
-                    // finger pi of C lies in [temp, K]  <=>  temp - C <= F - C <= D
+                    // finger pi of C lies in [temp, K]  <=>  temp - C <= F - C <= D: decided on the top 64
+                    // bits of the distances, on the exact keys only when they tie (F within 2^96 of K, of
+                    // temp or of C -- node-ID keys, IDs closer than 2^96)
                     A.row = L3.z;
-                    const K160 D = k_sub(K, C);
-                    const K160 dF = k_sub(A.k, C);
-                    bool hit = k_le(dF, D);
-                    if (hit) {
-                        if (gTx) hit = k_eq(dF, D);                        // temp == K
-                        else if (pi >= esl) hit = !k_zero(dF);             // 2^pi > temp - C
-                        else hit = cmp_gap(V, dF, gSL, C, ring_next(cur, (uint32_t)ns, V.n)) >= 0;
+                    const uint64_t Ft = top64_sub(A.k, C);
+                    const uint64_t Dk = SHARD ? top64(k_sub(K, C)) : Dt;
+                    bool hit;
+                    if (Ft != Dk && Ft != 0 && Ft != gSL) {
+                        // F != K: with temp == K no finger hits, and a finger that hits is short of K --
+                        // not responsible, as (pred F, F] lies inside (C, F]
+                        hit = Ft < Dk && !gTx && (pi >= esl || Ft > gSL);
+                    } else {
+                        const K160 D = k_sub(K, C);
+                        const K160 dF = k_sub(A.k, C);
+                        hit = k_le(dF, D);
+                        if (hit) {
+                            if (gTx) hit = k_eq(dF, D);                        // temp == K
+                            else if (pi >= esl) hit = !k_zero(dF);             // 2^pi > temp - C
+                            else hit = cmp_gap(V, dF, gSL, C, ring_next(cur, (uint32_t)ns, V.n)) >= 0;
+                        }
+                        nxt_sib = hit && k_eq(A.k, K);
                     }
                     if (hit) {
-                        // a finger short of K is not responsible: (pred F, F] lies inside (C, F]
-                        nxt = L1.y; nxt_sib = k_eq(A.k, K);
+                        nxt = L1.y;
                     } else if (--pi >= ilo) {
                         if (SHARD && remote && pi < KEYBITS - V.ftl) redo_hand();
                         else lp = fptr(pi);
@@ -826,9 +853,9 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                         nxt = fb; nxt_node = true;       // Chord.cc:653-658 (succ0 via 183-184 when temp == succ0)
                     }
                 } else {
-                    // PH_WIN: K inside the successor window; temp = farthest s_j <= K (Chord.cc:612-623)
-                    const K160 D = k_sub(K, C);
-                    const uint64_t Dt = top64(D);
+                    // PH_WIN: K inside the successor window; temp = farthest s_j <= K (Chord.cc:612-623),
+                    // on Dt = top64(K - C) kept from the arrival, the exact keys on a tie
+                    const uint64_t Dk = SHARD ? top64(k_sub(K, C)) : Dt;
                     const uint64_t g[8] = {u64(L0.x, L0.y), u64(L0.z, L0.w), u64(L1.x, L1.y), u64(L1.z, L1.w),
                                            u64(L2.x, L2.y), u64(L2.z, L2.w), u64(L3.x, L3.y), u64(L3.z, L3.w)};
                     int tj = -1;
@@ -838,8 +865,8 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                     #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         if (j < ns) {
-                            tie |= g[j] == Dt;
-                            if (g[j] < Dt) tj = j;
+                            tie |= g[j] == Dk;
+                            if (g[j] < Dk) tj = j;
                         }
                     }
                     bool tIsK = false;
@@ -860,7 +887,7 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                         // temp == K: temp if a finger points at it, else s_{tj-1}
                         gTx = true;
                         fb = ring_next(cur, (uint32_t)tj, V.n);
-                        pi = k_msb(D);
+                        pi = k_msb(k_sub(K, C));
                         if (pi >= ilo) {
                             lp = reinterpret_cast<const uint4*>(V.frow + (uint64_t)row + (uint32_t)(KEYBITS - 1 - pi));
                             ph = PH_PROBE;
@@ -921,6 +948,11 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
             if (arrived) {
                 uint32_t nx2 = NONE;
                 bool nx2_sib = false;
+                // the key's distance from the responder: the sibling test of a lookup's start and, for a
+                // responder that is not responsible, findNode's compares and first finger
+                const K160 D = k_sub(K, A.k);
+                // isSiblingFor(cur, K, 1): K in (pred, cur]  <=>  D == 0 or D > pred - cur (Chord.cc:452-457)
+                if (ph == PH_START) asib = k_zero(D) || cmp_gap(V, D, u64(L3.z, L3.w), A.k, cur == 0 ? V.n - 1 : cur - 1) > 0;
                 if (SHARD && redo) {
                     // a responder reached on another rank, which accounted for its response (or route
                     // message) and handed its decision here (record local byte 2)
@@ -939,8 +971,9 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                     if (asib) { fin = true; R = S; }
                 } else {
                     // FindNodeCall S->cur, FindNodeResponse cur->S (one NodeHandle)
-                    const int64_t cd = coord_ns(sx, sy, A.x, A.y, DC.round);
-                    const int64_t rtt = DC.msgCall + ((LKC && asib) ? DC.msgRespSib : DC.msgResp1) + 2 * cd;
+                    const int64_t cdr = coord_ns(sx, sy, A.x, A.y, DC.round);
+                    if (!SHARD) cd = cdr;
+                    const int64_t rtt = DC.msgCall + ((LKC && asib) ? DC.msgRespSib : DC.msgResp1) + 2 * cdr;
                     if (rtt >= DC.rpcTimeout) {
                         fin = true;
                         status = (t + DC.rpcTimeout > DC.lookupTimeout) ? OVS_LOOKUP_TIMEOUT : OVS_LOOKUP_RPC_TIMEOUT;
@@ -960,7 +993,7 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                 if (!fin) {
                     // findNode at cur for a key it is not responsible for (Chord.cc:583-674)
                     C = A.k; row = A.row; gSL = A.gSL; gTx = false;
-                    const K160 D = k_sub(K, C);
+                    if (!SHARD) Dt = top64(D);
                     const uint32_t s0 = ring_next(cur, 1, V.n);
                     if (cmp_gap(V, D, A.gS0, C, s0) <= 0) {
                         nx2 = s0; nx2_sib = true;                      // K in (C, succ0] (Chord.cc:583-590)
@@ -1009,8 +1042,9 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                     o.hops = (uint16_t)hops;
                     o.responsible = R;
                     o.one_way_hops = (uint8_t)(hops + (R != S ? 1 : 0));
-                    // sendRouteMessage to result[0] (BaseOverlay.cc:1107-1146); 0 delay to self
-                    o.latency_ns = t + ((R != S && !LKC) ? DC.msgRoute + coord_ns(sx, sy, A.x, A.y, DC.round) : 0);
+                    // sendRouteMessage to result[0] (BaseOverlay.cc:1107-1146); 0 delay to self.  R != S is
+                    // the responder whose response arrived this iteration: cd = coord_ns(S, R)
+                    o.latency_ns = t + ((R != S && !LKC) ? DC.msgRoute + (SHARD ? coord_ns(sx, sy, A.x, A.y, DC.round) : cd) : 0);
                 } else {
                     o.hops = (uint16_t)hops;
                     o.responsible = NONE;
@@ -1024,7 +1058,11 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                     io.stage_done[q] = dr;
                     io.stag[q] = (uint8_t)io.nsh;
                 } else {
-                    io.out[dst] = o;
+                    // the 16 B record as one store
+                    static_assert(sizeof(ovs_route_out) == 16 && alignof(ovs_route_out) == 8, "one 16 B record");
+                    reinterpret_cast<uint4*>(io.out)[dst] =
+                        make_uint4(o.responsible, (uint32_t)o.hops | ((uint32_t)o.status << 16) | ((uint32_t)o.one_way_hops << 24),
+                                   (uint32_t)(uint64_t)o.latency_ns, (uint32_t)((uint64_t)o.latency_ns >> 32));
                 }
                 active = false;
                 lp = nullptr;
