@@ -339,7 +339,10 @@ ovs_status  ovs_chord_export_tables(ovs_ctx* ctx, uint32_t* pred, uint32_t* succ
  * n*hopCountMax node indices (accepted responders in order, 0xFFFFFFFF padded).
  * rpcs may be NULL, else n FindNodeCall counts.  src[i] < n: a host-pointer call
  * returns OVS_EINVAL for a source outside the network; device-pointer calls do not
- * check (the caller's sources must be node indices). */
+ * check (the caller's sources must be node indices).  Koorde and explicit Chord
+ * tables (ovs_chord_load_tables) keep the accepted responders in that hop list as
+ * the lookup's visited set, so they need hopCountMax >= 1: hopCountMax = 0 (no
+ * hop limit) is OVS_ENOTSUP there. */
 ovs_status  ovs_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src,
                             uint64_t n, ovs_route_out* out, uint32_t* hop_seq, uint32_t* rpcs,
                             uint32_t flags, void* stream);

@@ -418,10 +418,13 @@ static uint32_t ft_getFinger(const orc_net* net, uint32_t node, uint32_t pos)   
  *    nextFinger = 0..159, trivial fingers (2^i <= succ - self) are removed, the
  *    others set to the node answering rpcFixfingers for self+2^i, i.e. the
  *    responsible node (Chord.cc:1228-1270, non-extended finger table). */
-static int check_params(const orc_params* p)
+static int check_params_sls(const orc_params* p, int slsMax)
 {
     /* the fixed capacities below (NVec 128 entries, 16 siblings) bound these parameters */
-    if (p->successorListSize < 1 || p->successorListSize > 120) { set_err("successorListSize must be 1..120"); return 0; }
+    if (p->successorListSize < 1 || p->successorListSize > slsMax) {
+        set_err(slsMax == 120 ? "successorListSize must be 1..120" : "koorde: successorListSize must be 1..255");
+        return 0;
+    }
     if (p->s < 1 || 5 * p->s > 120 || p->k < 1 || p->k > 64) { set_err("kademlia k must be 1..64, 5s <= 120"); return 0; }
     if (p->numSiblings < 0 || p->numSiblings > 16) { set_err("numSiblings must be 0..16"); return 0; }
     if (p->lookupRedundantNodes < 1 || p->lookupRedundantNodes > 64) { set_err("lookupRedundantNodes must be 1..64"); return 0; }
@@ -430,11 +433,14 @@ static int check_params(const orc_params* p)
     }
     return 1;
 }
+static int check_params(const orc_params* p) { return check_params_sls(p, 120); }
 
-static orc_net* chord_build(const orc_key* ids, uint32_t n, const double* xy, const orc_params* p, int lazy)
+/* slsMax: 120 for Chord (findNode answers whole successor lists in an NVec); Koorde's findNode
+ * answers one node and reads its lazy successor list by index, so its list may be longer */
+static orc_net* chord_build_sls(const orc_key* ids, uint32_t n, const double* xy, const orc_params* p, int lazy, int slsMax)
 {
     if (n < 2) { set_err("chord: need at least 2 nodes"); return NULL; }
-    if (!check_params(p)) return NULL;
+    if (!check_params_sls(p, slsMax)) return NULL;
     orc_net* net = net_alloc(NET_CHORD, ids, n, xy, p);
     if (!net) return NULL;
     uint32_t sls = (uint32_t)p->successorListSize;
@@ -463,6 +469,11 @@ static orc_net* chord_build(const orc_key* ids, uint32_t n, const double* xy, co
         }
     }
     return net;
+}
+
+static orc_net* chord_build(const orc_key* ids, uint32_t n, const double* xy, const orc_params* p, int lazy)
+{
+    return chord_build_sls(ids, n, xy, p, lazy, 120);
 }
 
 orc_net* orc_chord_build(const orc_key* ids, uint32_t n, const double* xy, const orc_params* p)
@@ -1359,7 +1370,7 @@ orc_net* orc_koorde_build(const orc_key* ids, uint32_t n, const double* xy, cons
         return NULL;
     }
     /* the Chord part as lazy stable tables: Koorde's findNode reads only pred and successors */
-    orc_net* net = chord_build(ids, n, xy, p, 1);
+    orc_net* net = chord_build_sls(ids, n, xy, p, 1, 255);
     if (!net) return NULL;
     net->type = NET_KOORDE;
     net->kdb = (uint32_t*)malloc(sizeof(uint32_t) * n);

@@ -665,7 +665,8 @@ hipError_t koorde_route(const KoordeTables& t, const KeyRec* recs, const double2
                         unsigned long long* dyn)
 {
     if (nq == 0) return hipSuccess;
-    if (!hopseq) return hipErrorInvalidValue;
+    // the hop list holds hopCountMax responders and is the visitOnlyOnce list: no limit, no list
+    if (!hopseq || hopCountMax < 1) return hipErrorInvalidValue;
     const KView kv = make_view(t, recs);
     // the chosen instantiation's occupancy-sized grid: static slices, with the dynamic tail when dyn is given
     auto launch = [&](auto k) {

@@ -1489,10 +1489,15 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
         if (st != OVS_OK) return st;
         if (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n))
             return fail(c, OVS_ESTATE, "context holds one arc of a sharded ring: use ovs_shard_step");
+        // explicit tables: the hop list (hopCountMax entries) is the lookup's visited set
+        if (!c->ideal && c->P.hopCountMax < 1)
+            return fail(c, OVS_ENOTSUP, "explicit Chord tables need hopCountMax >= 1 (the hop list is the visited set)");
         st = ensure_nodes(c, s);
         if (st != OVS_OK) return st;
     } else if (c->overlay == OVS_OVERLAY_KOORDE) {
         if (c->P.routingType != 0) return fail(c, OVS_ENOTSUP, "Koorde routing is implemented for routingType = iterative");
+        // the hop list (hopCountMax entries) is the visitOnlyOnce list: no hop limit leaves it without a size
+        if (c->P.hopCountMax < 1) return fail(c, OVS_ENOTSUP, "Koorde lookups need hopCountMax >= 1");
         if (c->P.lookupRedundantNodes != 1 || c->P.lookupParallelRpcs != 1 || c->P.lookupMerge ||
             c->P.numSiblings != 1 || !c->P.lookupVisitOnlyOnce)
             return fail(c, OVS_ENOTSUP,
@@ -1642,6 +1647,8 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
         if (st != OVS_OK) return st;
         if (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n))
             return fail(c, OVS_ESTATE, "context holds one arc of a sharded ring: LookupCall needs the whole ring");
+        if (!c->ideal && P.hopCountMax < 1)
+            return fail(c, OVS_ENOTSUP, "explicit Chord tables need hopCountMax >= 1 (the hop list is the visited set)");
         st = ensure_nodes(c, s);
         if (st != OVS_OK) return st;
     } else if (c->kad.lo != 0 || c->kad.hi != c->n) {

@@ -122,6 +122,60 @@ int main()
         route_some(net, p, 8);
         orc_net_free(net);
     }
+    // ---- oracle: Koorde on a crafted ring (runs of IDs under one 128-bit prefix with gaps of 1 and of
+    // 2^26 + small, node IDs 0 and 2^160 - 1) with successor / de Bruijn lists above 16: the shifts,
+    // the wrap-around and the list walks; then defaults and a short-list variant
+    {
+        const uint32_t n = 300;
+        Net p = population(n);
+        p.ids[0] = orc_key{{0, 0, 0, 0, 0}};
+        p.ids[n - 1] = orc_key{{~0u, ~0u, ~0u, ~0u, ~0u}};
+        const uint32_t gaps[4] = {1u, (1u << 26) + 1u, 3u, (1u << 26) + 2u};
+        for (uint32_t s : {20u, 100u, 200u}) {
+            uint32_t low = 1000u + s;
+            for (uint32_t j = 0; j < 18; ++j) {
+                p.ids[s + j] = p.ids[s];
+                p.ids[s + j].w[0] = low;
+                low += gaps[j % 4];
+            }
+        }
+        for (uint32_t i = 1; i < n; ++i) check(key_less(p.ids[i - 1], p.ids[i]), "crafted koorde ring sorted");
+        const int cfg[3][3] = {{40, 64, 4}, {16, 16, 4}, {4, 4, 2}};   // successorListSize, deBruijnListSize, shiftingBits
+        for (const auto& c : cfg) {
+            orc_params kp;
+            orc_params_koorde_default(&kp);
+            kp.successorListSize = c[0]; kp.deBruijnListSize = c[1]; kp.shiftingBits = c[2];
+            orc_net* net = orc_koorde_build(p.ids.data(), n, p.xy.data(), &kp);
+            check(net != nullptr, "koorde build");
+            std::vector<uint32_t> db(n), st(n);
+            std::vector<uint8_t> num(n);
+            orc_koorde_export(net, db.data(), st.data(), num.data());
+            // node-ID keys, their neighbours, the ring's ends and random keys from sources near the runs
+            std::vector<orc_key> keys;
+            std::vector<uint32_t> src;
+            for (uint32_t i = 0; i < n; ++i) {
+                orc_key k = p.ids[i], up = p.ids[i], dn = p.ids[i];
+                up.w[0] += 1; dn.w[0] -= 1;            // within the low word except at the ring's ends: still keys
+                for (const orc_key& x : {k, up, dn, orc_key{{rnd32(), rnd32(), rnd32(), rnd32(), rnd32()}}}) {
+                    keys.push_back(x); src.push_back((i + n - 5) % n);
+                    keys.push_back(x); src.push_back(rnd32() % n);
+                }
+            }
+            const uint64_t m = keys.size();
+            std::vector<orc_route_out> out(m);
+            std::vector<uint32_t> hop(m * 50), rpcs(m);
+            check(orc_route_batch(net, keys.data(), src.data(), m, out.data(), hop.data(), rpcs.data(), 2) != ORC_FAIL,
+                  "koorde route batch");
+            // direct findNode calls: fresh extensions, and steps around the key length (some throw)
+            for (uint32_t i = 0; i < 600; ++i) {
+                orc_key rk = p.ids[(src[i] + 1) % n];
+                int has = (int)(i & 1), step = has ? 150 + (int)(rnd32() % 20) : 1;
+                orc_koorde_find_node(net, src[i], &keys[i], &rk, &has, &step);
+            }
+            orc_clear_error();
+            orc_net_free(net);
+        }
+    }
     // ---- host .ini binder (oversim_amd/csrc/ovs_ini.cpp)
     ovs_params P;
     ovs_params_default(OVS_OVERLAY_CHORD, &P);

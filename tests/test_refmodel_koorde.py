@@ -2,7 +2,10 @@
 interval loops, the extension threaded through IterativeLookup) and refmodel.KoordeRing (Python
 integers, list walks by clockwise distance).  CPU only: the two readings agree on the de Bruijn
 state and on whole lookups over parameter variants, and the oracle reproduces the committed
-Koorde golden vectors (tests/golden/koorde_*.npz, generated with both readings in agreement)."""
+Koorde golden vectors (tests/golden/koorde_*.npz, generated with both readings in agreement).
+They also agree on every input of tests/test_gpu_koorde_paths.py (tests/koorde_rings.py): list
+sizes above 16, the crafted rings with their steered findNode calls and census, the tiny rings
+and the ring holding 0 and 2^160 - 1, and the finish-status parameter sets."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -10,6 +13,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import koorde_rings as KR
 import refmodel
 from oracle_lib import OracleNet, koorde_params
 from oversim_amd import Params, workload as W
@@ -41,6 +45,117 @@ def test_oracle_agrees_with_refmodel(n, sls, dbls, sb, uo, us, seed):
         for f in FIELDS:
             assert int(r[f][i]) == int(m[f]), (i, f, r[f][i], m[f])
         assert [int(x) for x in r["hop_seq"][i] if x != 0xFFFFFFFF] == m["hop_seq"], i
+
+
+# ---- the inputs of tests/test_gpu_koorde_paths.py: both readings must agree on them first
+
+def _ring(net, **kw):
+    p = koorde_params(**kw)
+    o = OracleNet("koorde", net.ids, net.xy, p)
+    R = refmodel.KoordeRing(net.ids, net.xy, p.successorListSize, p.deBruijnListSize, p.shiftingBits,
+                            bool(p.useOtherLookup), bool(p.useSucList), rnd=bool(p.simtimeRound))
+    db, st, num = o.koorde_state()
+    for v in range(len(net.ids)):
+        dbn, dbl = R.db[v]
+        assert (db[v], st[v], num[v]) == (dbn, dbl[0], len(dbl)), v
+    return o, R, p
+
+
+def _same_lookups(o, R, p, keys, src, stride=1):
+    """Every stride-th lookup in the Python reading against the oracle's whole batch."""
+    r = o.route(keys, src, record_hops=True)
+    for i in range(0, len(keys), stride):
+        m = R.lookup(keys[i], int(src[i]), hop_max=p.hopCountMax, lk_to=p.lookupTimeout)
+        for f in FIELDS:
+            assert int(r[f][i]) == int(m[f]), (i, f, r[f][i], m[f])
+        assert [int(x) for x in r["hop_seq"][i] if x != 0xFFFFFFFF] == m["hop_seq"], i
+    return r
+
+
+def _same_find_node(o, R, node, keys, rks, steps):
+    """Direct findNode calls with given extensions (rks None: fresh): next hop, route key, step."""
+    ans = []
+    for i in range(len(node)):
+        rk = None if rks is None else rks[i]
+        h, rko, st = o.koorde_find_node(int(node[i]), keys[i], rk, 1 if steps is None else int(steps[i]))
+        try:
+            mh, mext = R.find_node(int(node[i]), KR.ints(keys[i])[0], [None if rk is None else KR.ints(rk)[0],
+                                                                         1 if steps is None else int(steps[i])])
+        except ValueError:
+            mh = None
+        assert h == mh, (i, h, mh)
+        if h is not None:
+            assert (None if rko is None else KR.ints(rko)[0], st) == (mext[0], mext[1]), i
+        ans.append(h)
+    return ans
+
+
+@pytest.mark.parametrize("variant", list(KR.LIST_WALK))
+def test_list_sizes_above_16(variant):
+    net = W.population(3000, 30)
+    kw = KR.LIST_WALK[variant]
+    assert kw.get("shiftingBits", 4) in KR.SAFE_SB or KR.min_gap(net) >= 1 << 16
+    o, R, p = _ring(net, **kw)
+    keys, src = KR.mixed_lookups(net, 6000, 31)
+    _same_lookups(o, R, p, keys, src)
+    node, fk = KR.chain_inputs(net, 1000, 32)
+    _same_find_node(o, R, node, fk, None, None)
+    node, fk, rk, steps = KR.past_key_length_inputs(net, 1000, 33)
+    assert None in _same_find_node(o, R, node, fk, rk, steps)
+
+
+def test_list_walk_on_a_12_node_ring():
+    net = KR.tiny_ring(12, 34)
+    o, R, p = _ring(net, deBruijnListSize=32)
+    keys, src = KR.edge_lookups(net, 35)
+    _same_lookups(o, R, p, keys, src)
+
+
+@pytest.mark.parametrize("kw", [{}, dict(shiftingBits=2)], ids=["default", "sb2"])
+@pytest.mark.parametrize("n", [17, 40, 1000])
+def test_crafted_rings(n, kw):
+    net, runs = KR.crafted_ring(n, 50 + n)
+    o, R, p = _ring(net, **kw)
+    keys, src = KR.crafted_lookups(net, runs, 60 + n)
+    assert len(keys) <= 10_000
+    _same_lookups(o, R, p, keys, src)
+    c = KR.census(net, 16, src, keys)
+    assert min(c.values()) > 0, c
+    node, sk, rk, steps = KR.steered_calls(net, runs, p.shiftingBits)
+    assert len(node) <= 2000
+    ans = _same_find_node(o, R, node, sk, rk, steps)
+    c2 = KR.census(net, 16, node, sk)
+    _, st, num = o.koorde_state()
+    assert KR.steered_census(net, runs, ans, st, num, node) > 0, c2
+
+
+@pytest.mark.parametrize("kw", [{}, dict(successorListSize=4, deBruijnListSize=4, shiftingBits=2)], ids=["default", "4_4_sb2"])
+@pytest.mark.parametrize("n", [2, 3, 5, 17, "edge40"])
+def test_tiny_rings_and_wrap_around(n, kw):
+    net = KR.edge_ring() if n == "edge40" else KR.tiny_ring(n, 70 + n)
+    o, R, p = _ring(net, **kw)
+    keys, src = KR.edge_lookups(net, 80)
+    _same_lookups(o, R, p, keys, src)
+
+
+@pytest.mark.parametrize("kw", [dict(hopCountMax=1), dict(hopCountMax=3), dict(simtimeRound=0), dict(simtimeRound=1),
+                                dict(lookupTimeout=10.0, wide=1), dict(lookupTimeout=3.0, wide=1), dict(shiftingBits=1)],
+                         ids=["hcm1", "hcm3", "rnd0", "rnd1", "wide_lt10", "wide_lt3", "sb1"])
+def test_finish_statuses_and_parameters(kw):
+    kw = dict(kw)
+    net = W.population(1000, 90)
+    if kw.pop("wide", 0):
+        net = KR.Network(ids=net.ids, xy=np.random.default_rng(902).uniform(-450.0, 450.0, size=net.xy.shape))
+    o, R, p = _ring(net, **kw)
+    keys, src = KR.mixed_lookups(net, 6000, 91)
+    r = _same_lookups(o, R, p, keys, src)
+    seen = set(int(x) for x in r["status"])
+    if "hopCountMax" in kw:
+        assert {0, 3} <= seen
+    if "lookupTimeout" in kw:
+        assert (2 if kw["lookupTimeout"] == 10.0 else 1) in seen and 0 in seen
+    if "shiftingBits" in kw:
+        assert (r["hops"] > 16).any()
 
 
 @pytest.mark.parametrize("name", ["koorde_n2000", "koorde_n2000_sb2_nosuc"])
