@@ -529,6 +529,88 @@ ovs_status  ovs_kbrtest_lookup_stats_batch(ovs_ctx* ctx, const ovs_lookup_out* o
                                            double failure_latency_s, ovs_kbrtest_lookup_stats* stats,
                                            uint32_t flags, void* stream);
 
+/* ---- KBRTestApp RPC test (kbrRpcTest = true; additive to ABI 12; test OVS_HAS_KBR_RPC_TEST) ----
+ * Replaces, for a batch of routed KbrTestCall round trips:
+ *   KBRTestApp::handleTimerEvent, rpcTimer       src/applications/kbrtestapp/KBRTestApp.cc:172-189
+ *     KbrTestCall of testMsgSize bytes -> sendRouteRpcCall(TIER1_COMP, destKey, call, context)
+ *   BaseRpc::sendRpcCall                          src/common/BaseRpc.cc:173-274 (ROUTE_TRANSPORT, timeout
+ *     rpcKeyTimeout 202-205, retries 0; the timeout self-message is scheduled at send time, 257-258)
+ *   BaseApp::internalSendRouteRpc / callRoute     src/common/BaseApp.cc:564-570, 241-281
+ *   BaseOverlay::route -> sendToKey               src/common/BaseOverlay.cc:1310-1359
+ *   KBRTestApp::kbrTestCall                       KBRTestApp.cc:230-235 (KbrTestResponse of the call's length)
+ *   BaseApp::internalSendRpcResponse              BaseApp.cc:572-611
+ *   BaseRpc::sendRpcResponse                      BaseRpc.cc:531-596 (callHopCount, 570)
+ *   KBRTestApp::handleRpcResponse / handleRpcTimeout   KBRTestApp.cc:237-329
+ * The call leg is the one-way route of ovs_route_batch: the same wrappers (BaseAppDataMessage +
+ * BaseRouteMessage) around a testMsgSize-byte payload, so its arrival time, hop count and answering
+ * node are that call's latency_ns, one_way_hops and responsible.  The response leg: under iterative
+ * and semi-recursive routing the KbrTestResponse goes straight back to the caller by UDP
+ * (BaseOverlay.cc:1340-1341: testMsgSize + BASEAPPDATA_L (5 B) + 28 B UDP/IP on the wire, hop count 1,
+ * BaseOverlay.cc:751; to the node itself: no delay and hop count 0); under full-recursive routing it is
+ * routed hop by hop to the caller's own key (BaseApp.cc:595-599), a second recursive route from the
+ * responder.  measureAuthBlock does not enter: the response's length is set with setByteLength.  An
+ * RPC whose response arrives at or after rpcKeyTimeout times out (the timeout event is scheduled first),
+ * as does one whose call route, or return route, is dropped or ends at another node. */
+#define OVS_HAS_KBR_RPC_TEST 1
+enum { OVS_RPC_ANSWERED = 0, OVS_RPC_TIMEOUT = 1 };
+typedef struct ovs_rpc_out {        /* 32 B */
+    uint32_t responder;             /* node that answered the call (sorted-ID order); 0xFFFFFFFF when none */
+    uint16_t hop_count;             /* "KBRTestApp: RPC Hop Count" = callHopCount + the response's hop count
+                                       (KBRTestApp.cc:271-274); 0 on timeout */
+    uint8_t  call_hops;             /* KbrTestResponse callHopCount: the call route's one_way_hops; 0 when none answered */
+    uint8_t  status;                /* the call route's OVS_LOOKUP_* */
+    uint8_t  outcome;               /* OVS_RPC_ANSWERED / OVS_RPC_TIMEOUT (handleRpcResponse / handleRpcTimeout) */
+    uint8_t  resp_status;           /* full-recursive routing: the return route's OVS_LOOKUP_*; 0 otherwise */
+    uint8_t  pad[6];                /* 0 */
+    int64_t  rtt_ns;                /* response arrival - send time, ns; -1 on timeout */
+    int64_t  call_latency_ns;       /* the call's arrival at the responder (ovs_route_out.latency_ns); -1 when none */
+} ovs_rpc_out;
+
+/* Batched KbrTestCalls: RPC i is sent by node src[i] to keys[i].  Accepted: everything
+ * ovs_route_batch accepts on an unsharded context with routingType 0, 1 or 2 (the call leg takes that
+ * call's path and checks, so its refusals are inherited); routingType 4 is OVS_ENOTSUP (the response
+ * would follow the recorded hops back, BaseRpc.cc:576-584), as is 3.  Buffers follow `flags`; sources
+ * as ovs_route_batch (host calls check them before anything is staged).  The device-pointer form is
+ * asynchronous on `stream`: route, finish pass and return route are queued without a host
+ * synchronisation. */
+ovs_status  ovs_rpc_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                          ovs_rpc_out* out, uint32_t flags, void* stream);
+
+/*   KBRTestApp::handleRpcResponse / handleRpcTimeout   KBRTestApp.cc:251-314
+ *     delivered = answered && (!lookupNodeIds || the responder is the node owning destKey);
+ *     recordOutVector("KBRTestApp: RPC Success Latency" / "RPC Total Latency" / "RPC Hop Count");
+ *     wrong node or timeout: numRpcDropped, "RPC Total Latency" = failureLatency
+ *   KBRTestApp::finishApp                               KBRTestApp.cc:519-545 */
+typedef struct ovs_kbrtest_rpc_stats {
+    uint64_t num_sent;               /* numRpcSent (= RPCs in the batch) */
+    uint64_t num_delivered;          /* numRpcDelivered */
+    uint64_t num_dropped;            /* numRpcDropped: answered by another node (lookupNodeIds) or timed out */
+    uint64_t num_timeout;            /* the timed-out part of num_dropped */
+    uint64_t bytes_sent, bytes_delivered, bytes_dropped;
+    uint64_t hop_count_sum;          /* "RPC Hop Count" over delivered RPCs */
+    int64_t  success_latency_sum_ns; /* "RPC Success Latency" */
+    uint32_t hop_count_min, hop_count_max;
+    int64_t  success_latency_min_ns, success_latency_max_ns;
+    double   hop_count_mean;         /* "Vector: KBRTestApp: RPC Hop Count.mean" */
+    double   success_latency_mean_s; /* "Vector: KBRTestApp: RPC Success Latency.mean" */
+    double   total_latency_mean_s;   /* "Vector: KBRTestApp: RPC Total Latency.mean" */
+    uint64_t status_count[8];        /* RPCs by the call route's OVS_LOOKUP_* status */
+    uint64_t hop_hist[64];           /* delivered RPCs by RPC hop count (63 = 63 or more) */
+    ovs_stddev delivered_msgs_per_s; /* "KBRTestApp: RPC Delivered Messages/s" */
+    ovs_stddev delivered_bytes_per_s;
+    ovs_stddev dropped_msgs_per_s;
+    ovs_stddev dropped_bytes_per_s;
+    ovs_stddev delivery_ratio;       /* "KBRTestApp: RPC Delivery Ratio" ((float)d / (float)s) */
+} ovs_kbrtest_rpc_stats;
+
+/* Reduce a batch of RPC results (out/keys/src as passed to ovs_rpc_batch) to the KBRTestApp RPC
+ * statistics; measured_time_s, lookup_node_ids and failure_latency_s as for
+ * ovs_kbrtest_lookup_stats_batch (both times must be >= 0).  *stats is host memory. */
+ovs_status  ovs_kbrtest_rpc_stats_batch(ovs_ctx* ctx, const ovs_rpc_out* out, const ovs_key160* keys,
+                                        const uint32_t* src, uint64_t n, double measured_time_s,
+                                        int32_t lookup_node_ids, double failure_latency_s,
+                                        ovs_kbrtest_rpc_stats* stats, uint32_t flags, void* stream);
+
 /* ---- Chord overlay broadcast (additive to ABI 12; test OVS_HAS_CHORD_BROADCAST) ----
  * Replaces, for a batch of broadcasts on a converged ring (ovs_chord_load):
  *   BroadcastTestApp::initBroadcast / rpcBroadcastRequest  src/tier2/broadcasttestapp/BroadcastTestApp.cc:197-340

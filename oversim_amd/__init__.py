@@ -6,8 +6,9 @@ the reference's BaseOverlay / AbstractLookup interface (kbr.py) plus workload
 generation (workload.py).
 """
 from .kbr import (BCAST_NODE_DTYPE, DEVICE_PTRS, LOOKUP_OUT_DTYPE, LOOKUP_STATUS, NONE, OVERLAY_CHORD,  # noqa: F401
-                  OVERLAY_KADEMLIA, ROUTE_OUT_DTYPE, BcastStats, KbrEngine, KbrError, Network, Params, key_from_int, key_to_int, keys_array, lib)
+                  OVERLAY_KADEMLIA, ROUTE_OUT_DTYPE, RPC_OUT_DTYPE, BcastStats, KbrEngine, KbrError, KbrTestRpcStats, Network, Params,
+                  key_from_int, key_to_int, keys_array, lib)
 
 __all__ = ["KbrEngine", "KbrError", "Params", "Network", "lib", "keys_array", "key_from_int", "key_to_int",
            "OVERLAY_CHORD", "OVERLAY_KADEMLIA", "ROUTE_OUT_DTYPE", "LOOKUP_OUT_DTYPE", "LOOKUP_STATUS", "NONE", "DEVICE_PTRS",
-           "BCAST_NODE_DTYPE", "BcastStats"]
+           "BCAST_NODE_DTYPE", "BcastStats", "RPC_OUT_DTYPE", "KbrTestRpcStats"]

@@ -25,6 +25,7 @@
 #include "host_tables.hpp"
 #include "kad.hpp"
 #include "kad_shard.hpp"
+#include "kbr_rpc.hpp"
 #include "koorde.hpp"
 #include "launch.hpp"
 #include "persist.hpp"
@@ -77,6 +78,7 @@ struct ovs_ctx {
     // histograms, one allocation shared by the calls on this context like kvis
     CachedBuf ks;
     CachedBuf bq;                        // the broadcast's item queue (ovs_chord_broadcast_batch), cached like kvis
+    CachedBuf rpcb;                      // the RPC test's route records and return-route inputs (ovs_rpc_batch)
     DynSlots dyn;                        // the persistent route kernels' dynamic-tail counters (dyn_acquire)
     // multi-GPU Kademlia: this rank's in-flight lookups (ovs_kad_shard_begin)
     void* kst = nullptr;                 // KadLookup<alpha> state records
@@ -168,6 +170,7 @@ void free_tables(ovs_ctx* c)
     c->kvis.free();
     c->ks.free();
     c->bq.free();
+    c->rpcb.free();
     c->overlay = 0; c->n = 0; c->nfing = 0;
     c->bbox_ok = false;
     c->ch.clear();
@@ -482,6 +485,7 @@ void ovs_ctx_destroy(ovs_ctx* c)
     c->kvis.destroy();
     c->ks.destroy();
     c->bq.destroy();
+    c->rpcb.destroy();
     c->dyn.destroy();
     if (c->route_scratch && c->route_scratch_release) c->route_scratch_release(c->route_scratch);
     for (auto& kv : c->stage) stage_free(kv.second);
@@ -2246,6 +2250,159 @@ ovs_status ovs_kbrtest_lookup_stats_batch(ovs_ctx* c, const ovs_lookup_out* out,
     finish_stddev(r, 0, o.successful_lookups_per_s);
     finish_stddev(r, 2, o.failed_lookups_per_s);
     finish_stddev(r, 4, o.success_ratio);
+    return OVS_OK;
+}
+
+// KBRTestApp RPC test (KBRTestApp.cc:172-189, 230-329): the call leg is ovs_route_batch itself, on this
+// call's staged copies, so its checks and messages are inherited; k_rpc_finish adds the response leg and
+// the timeout rule; full-recursive routing routes the responses back (BaseApp.cc:595-599) and folds them
+// in.  Everything is queued on one stream with no host synchronisation in between.
+ovs_status ovs_rpc_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_rpc_out* out,
+                         uint32_t flags, void* stream)
+{
+    static_assert(sizeof(ovs_rpc_out) == 32, "ovs_rpc_out is 32 B");
+    if (!c || (!keys && n) || (!src && n) || (!out && n)) return OVS_EINVAL;
+    // the route's own refusals (no network, EpiChord, an arc of a sharded network, parameters), before
+    // anything is staged: an empty batch runs exactly its checks
+    ovs_status st = ovs_route_batch(c, keys, src, 0, nullptr, nullptr, nullptr, flags, stream);
+    if (st != OVS_OK) return st;
+    if (c->P.routingType == 4)
+        return fail(c, OVS_ENOTSUP, "KbrTestCall under source-routing-recursive routing: the response follows the "
+                                    "call's recorded hops back (BaseRpc.cc:576-584), which is not implemented");
+    if (c->P.routingType < 0 || c->P.routingType > 2)
+        return fail(c, OVS_ENOTSUP, "KbrTestCall is implemented for routingType iterative / semi-recursive / full-recursive");
+    if (!(c->P.rpcKeyTimeout >= 0)) return fail(c, OVS_EINVAL, "rpcKeyTimeout must be >= 0");
+    if (n == 0) return OVS_OK;
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    st = check_sources(c, src, n, dev);
+    if (st != OVS_OK) return st;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    const bool full = c->P.routingType == 2;
+    CallFrame F(dev, s);
+    const ovs_key160* dk = F.in(keys, n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_rpc_out* dout = F.out(out, n);
+    if (!F.ok()) return frame_fail(c, F);
+    // route records (16 B), and for the return route its keys (20 B) and sources (4 B), each part 256 B aligned
+    const uint64_t o_keys = (sizeof(ovs_route_out) * n + 255) & ~255ull;
+    const uint64_t o_src = o_keys + ((sizeof(K160) * n + 255) & ~255ull);
+    CachedBuf::Lease buf = c->rpcb.acquire(full ? o_src + sizeof(uint32_t) * n : o_keys, s);
+    if (!buf) return lease_fail(c, "RPC buffers", buf);
+    ovs_route_out* droute = reinterpret_cast<ovs_route_out*>(buf.data());
+    K160* rkeys = full ? reinterpret_cast<K160*>(buf.data() + o_keys) : nullptr;
+    uint32_t* rsrc = full ? reinterpret_cast<uint32_t*>(buf.data() + o_src) : nullptr;
+    st = ovs_route_batch(c, dk, ds, n, droute, nullptr, nullptr, OVS_DEVICE_PTRS, s);
+    if (st != OVS_OK) return st;
+    RpcConsts RC{};
+    const DelayConsts DC = delay_consts(c->P);
+    RC.timeout = simtime_host(c->P.rpcKeyTimeout, c->P.simtimeRound);
+    // KbrTestResponse in a BaseAppDataMessage straight over UDP: payload + BASEAPPDATA_L 40 bits + UDP/IP 28 B
+    // (BaseOverlay.cc:1340-1341, CommonMessages.msg:68, SimpleUDP.cc:291)
+    RC.respMsg = 2 * simtime_host((double)((int64_t)(c->P.testMsgSize + 5 + 28) * 8) / c->P.datarate, c->P.simtimeRound) +
+                 DC.access2;
+    RC.round = c->P.simtimeRound;
+    RC.full = full;
+    RC.nnodes = (uint32_t)c->n;
+    hipError_t e = launch_rpc_finish(droute, ds, c->recs, c->xy, RC, n, dout, rkeys, rsrc, c->num_cu, s);
+    if (e != hipSuccess) return hip_fail(c, e, "RPC finish kernel");
+    if (full) {
+        // the return routes overwrite the call routes: what the fold needs of those is in dout
+        st = ovs_route_batch(c, reinterpret_cast<const ovs_key160*>(rkeys), rsrc, n, droute, nullptr, nullptr,
+                             OVS_DEVICE_PTRS, s);
+        if (st != OVS_OK) return st;
+        e = launch_rpc_fold(droute, ds, RC, n, dout, c->num_cu, s);
+        if (e != hipSuccess) return hip_fail(c, e, "RPC fold kernel");
+    }
+    buf.release();
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
+    return OVS_OK;
+}
+
+ovs_status ovs_kbrtest_rpc_stats_batch(ovs_ctx* c, const ovs_rpc_out* out, const ovs_key160* keys, const uint32_t* src,
+                                       uint64_t n, double measured_time_s, int32_t lookup_node_ids,
+                                       double failure_latency_s, ovs_kbrtest_rpc_stats* stats, uint32_t flags,
+                                       void* stream)
+{
+    if (!c || !stats || (n && (!out || !src || (lookup_node_ids && !keys)))) return OVS_EINVAL;
+    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
+    if (!(measured_time_s >= 0)) return fail(c, OVS_EINVAL, "measured_time_s must be >= 0");
+    if (!(failure_latency_s >= 0)) return fail(c, OVS_EINVAL, "failure_latency_s must be >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    CallFrame F(dev || n == 0, s);                            // an empty batch has nothing to stage
+    const ovs_rpc_out* dout = F.in(out, n);
+    const uint32_t* ds = F.in(src, n);
+    const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
+    RpcStatsDev* S = F.scratch<RpcStatsDev>(1);
+    uint32_t* counts = F.scratch<uint32_t>(3 * c->n);
+    if (!F.ok()) return frame_fail(c, F);
+    RpcStatsDev h{};
+    std::vector<uint32_t> nc;
+    try {
+        nc.resize(3 * c->n);
+    } catch (const std::bad_alloc&) {
+        return fail(c, OVS_ENOMEM, "per-node counters");
+    }
+    hipError_t e = launch_rpc_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids, S, counts, c->num_cu, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(nc.data(), counts, sizeof(uint32_t) * nc.size(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(c, e, "RPC statistics kernel");
+
+    ovs_kbrtest_rpc_stats& o = *stats;
+    std::memset(&o, 0, sizeof o);
+    const uint64_t B = (uint64_t)c->P.testMsgSize;
+    o.num_sent = n;
+    o.num_delivered = h.delivered;
+    o.num_dropped = h.dropped;
+    o.num_timeout = h.timeout;
+    o.bytes_sent = n * B;
+    o.bytes_delivered = h.delivered * B;
+    o.bytes_dropped = h.dropped * B;
+    o.hop_count_sum = h.hop_sum;
+    o.success_latency_sum_ns = (int64_t)h.lat_sum;
+    if (h.delivered) {
+        o.hop_count_min = (uint32_t)h.hop_min;
+        o.hop_count_max = (uint32_t)h.hop_max;
+        o.success_latency_min_ns = (int64_t)h.lat_min;
+        o.success_latency_max_ns = (int64_t)h.lat_max;
+        o.hop_count_mean = (double)h.hop_sum / (double)h.delivered;
+        o.success_latency_mean_s = ((double)h.lat_sum / (double)h.delivered) * 1e-9;
+    }
+    // "RPC Total Latency": rtt for delivered RPCs, failureLatency for the others (KBRTestApp.cc:262-263, 281-285, 306-310)
+    if (n) o.total_latency_mean_s = ((double)h.lat_sum * 1e-9 + (double)h.dropped * failure_latency_s) / (double)n;
+    for (int i = 0; i < 8; ++i) o.status_count[i] = h.status[i];
+    for (int i = 0; i < 64; ++i) o.hop_hist[i] = h.hist[i];
+    // KBRTestApp::finishApp (KBRTestApp.cc:519-545) at every node, in node order: cStdDev::collect
+    // (count, sum, sum of squares, min, max); only from GlobalStatistics::MIN_MEASURED = 0.1 s on (502)
+    if (measured_time_s >= 0.1) {
+        double r[NSTAT * 5];
+        uint64_t cnt[NSTAT] = {0, 0, 0, 0, 0};
+        for (int k = 0; k < NSTAT; ++k) {
+            r[k * 5 + 0] = 0; r[k * 5 + 1] = 0; r[k * 5 + 2] = INFINITY; r[k * 5 + 3] = -INFINITY;
+        }
+        auto add = [&](int k, double v) {
+            r[k * 5 + 0] += v;
+            r[k * 5 + 1] += v * v;
+            if (v < r[k * 5 + 2]) r[k * 5 + 2] = v;
+            if (v > r[k * 5 + 3]) r[k * 5 + 3] = v;
+            ++cnt[k];
+        };
+        const uint64_t N = c->n;
+        for (uint64_t v = 0; v < N; ++v) {
+            const uint32_t sent = nc[v], d = nc[N + v], dr = nc[2 * N + v];
+            add(0, (double)d / measured_time_s);
+            add(1, (double)((uint64_t)d * B) / measured_time_s);
+            add(2, (double)dr / measured_time_s);
+            add(3, (double)((uint64_t)dr * B) / measured_time_s);
+            if (sent > 0) add(4, (double)((float)d / (float)sent));
+        }
+        for (int k = 0; k < NSTAT; ++k) std::memcpy(&r[k * 5 + 4], &cnt[k], sizeof(uint64_t));
+        ovs_stddev* sd[NSTAT] = {&o.delivered_msgs_per_s, &o.delivered_bytes_per_s, &o.dropped_msgs_per_s,
+                                 &o.dropped_bytes_per_s, &o.delivery_ratio};
+        for (int k = 0; k < NSTAT; ++k) finish_stddev(r, k, *sd[k]);
+    }
     return OVS_OK;
 }
 

@@ -135,6 +135,11 @@ LOOKUP_OUT_DTYPE = np.dtype([("num_siblings", "<u4"), ("hops", "<u2"), ("status"
 assert LOOKUP_OUT_DTYPE.itemsize == 16
 BCAST_NODE_DTYPE = np.dtype([("arrival_ns", "<i8"), ("parent", "<u4"), ("hops", "<u2"), ("rank", "<u2")])
 assert BCAST_NODE_DTYPE.itemsize == 16
+RPC_OUT_DTYPE = np.dtype([("responder", "<u4"), ("hop_count", "<u2"), ("call_hops", "u1"), ("status", "u1"),
+                          ("outcome", "u1"), ("resp_status", "u1"), ("pad", "u1", 6), ("rtt_ns", "<i8"),
+                          ("call_latency_ns", "<i8")])
+assert RPC_OUT_DTYPE.itemsize == 32
+RPC_ANSWERED, RPC_TIMEOUT = 0, 1
 
 class StdDev(C.Structure):
     """ovs_stddev: one cStdDev summary (GlobalStatistics::addStdDev)."""
@@ -244,6 +249,8 @@ def lib() -> C.CDLL:
         "ovs_kad_maintenance_round": ([vp, vp, u64, vp, vp, vp], C.c_int),
         "ovs_kbrtest_lookup_stats_batch": ([vp, vp, vp, i32, vp, vp, u64, C.c_double, i32, C.c_double, vp, u32, vp],
                                            C.c_int),
+        "ovs_rpc_batch": ([vp, vp, vp, u64, vp, u32, vp], C.c_int),
+        "ovs_kbrtest_rpc_stats_batch": ([vp, vp, vp, vp, u64, C.c_double, i32, C.c_double, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -312,6 +319,30 @@ class KbrTestLookupStats(C.Structure):
         "successful_lookups_per_s": "KBRTestApp: Successful Lookups/s",
         "failed_lookups_per_s": "KBRTestApp: Failed Lookups/s",
         "success_ratio": "KBRTestApp: Lookup Success Ratio",
+    }
+
+
+class KbrTestRpcStats(C.Structure):
+    """ovs_kbrtest_rpc_stats: KBRTestApp RPC-test statistics of a batch (KBRTestApp.cc:251-314, 519-545)."""
+
+    _fields_ = [
+        ("num_sent", C.c_uint64), ("num_delivered", C.c_uint64), ("num_dropped", C.c_uint64),
+        ("num_timeout", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_delivered", C.c_uint64),
+        ("bytes_dropped", C.c_uint64), ("hop_count_sum", C.c_uint64), ("success_latency_sum_ns", C.c_int64),
+        ("hop_count_min", C.c_uint32), ("hop_count_max", C.c_uint32),
+        ("success_latency_min_ns", C.c_int64), ("success_latency_max_ns", C.c_int64),
+        ("hop_count_mean", C.c_double), ("success_latency_mean_s", C.c_double), ("total_latency_mean_s", C.c_double),
+        ("status_count", C.c_uint64 * 8), ("hop_hist", C.c_uint64 * 64),
+        ("delivered_msgs_per_s", StdDev), ("delivered_bytes_per_s", StdDev),
+        ("dropped_msgs_per_s", StdDev), ("dropped_bytes_per_s", StdDev), ("delivery_ratio", StdDev),
+    ]
+
+    STDDEV_NAMES = {
+        "delivered_msgs_per_s": "KBRTestApp: RPC Delivered Messages/s",
+        "delivered_bytes_per_s": "KBRTestApp: RPC Delivered Bytes/s",
+        "dropped_msgs_per_s": "KBRTestApp: RPC Dropped Messages/s",
+        "dropped_bytes_per_s": "KBRTestApp: RPC Dropped Bytes/s",
+        "delivery_ratio": "KBRTestApp: RPC Delivery Ratio",
     }
 
 
@@ -750,6 +781,45 @@ class KbrEngine:
                                                          _ptr(src), len(out), float(measured_time_s),
                                                          int(bool(lookupNodeIds)), float(failureLatency),
                                                          C.byref(st), 0, None), "ovs_kbrtest_lookup_stats_batch")
+        return st
+
+    # -- KBRTestApp RPC test
+    def rpcCall(self, keys, src) -> dict:
+        """Batched routed KbrTestCall round trips (KBRTestApp with kbrRpcTest; KBRTestApp.cc:172-189,
+        230-329): RPC i from node src[i] to keys[i].  Returns the ovs_rpc_out fields as arrays."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        out = np.empty(n, dtype=RPC_OUT_DTYPE)
+        self._chk(self._L.ovs_rpc_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), 0, None), "ovs_rpc_batch")
+        return {f: out[f].copy() for f in RPC_OUT_DTYPE.names}
+
+    def rpc_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
+        """Device-resident RPC batch (pointers on this context's device, async on `stream`, 0 = default stream)."""
+        self._chk(self._L.ovs_rpc_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n, C.c_void_p(out_ptr),
+                                        DEVICE_PTRS, C.c_void_p(stream) if stream else None), "ovs_rpc_batch")
+
+    def kbrtest_rpc_stats(self, result: dict | np.ndarray, keys, src, measured_time_s: float,
+                          lookupNodeIds: bool = True, failureLatency: float = 10.0) -> KbrTestRpcStats:
+        """Reduce rpcCall() results to the KBRTestApp RPC-test statistics on the device."""
+        if isinstance(result, dict):
+            out = np.zeros(len(result["responder"]), dtype=RPC_OUT_DTYPE)
+            for f in RPC_OUT_DTYPE.names:
+                if f in result:
+                    out[f] = result[f]
+        else:
+            out = np.ascontiguousarray(result, dtype=RPC_OUT_DTYPE)
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        if not (len(out) == len(keys) == len(src)):
+            raise ValueError("result, keys and src differ in length")
+        st = KbrTestRpcStats()
+        self._chk(self._L.ovs_kbrtest_rpc_stats_batch(self._h, _ptr(out), _ptr(keys), _ptr(src), len(out),
+                                                      float(measured_time_s), int(bool(lookupNodeIds)),
+                                                      float(failureLatency), C.byref(st), 0, None),
+                  "ovs_kbrtest_rpc_stats_batch")
         return st
 
     def kbrtest_stats_device(self, out_ptr: int, keys_ptr: int, src_ptr: int, n: int, measured_time_s: float,
