@@ -611,6 +611,158 @@ ovs_status  ovs_kbrtest_rpc_stats_batch(ovs_ctx* ctx, const ovs_rpc_out* out, co
                                         int32_t lookup_node_ids, double failure_latency_s,
                                         ovs_kbrtest_rpc_stats* stats, uint32_t flags, void* stream);
 
+/* ---- DHT tier: batched put / get on a stable network (additive to ABI 12; test OVS_HAS_DHT) ----
+ * Replaces, for a batch of independent DHT operations:
+ *   DHT::handlePutCAPIRequest / sendPutLookupCall     src/applications/dht/DHT.cc:499-516
+ *   DHT::handleGetCAPIRequest / sendGetLookupCall     DHT.cc:518-535
+ *   DHT::handleLookupResponse                         DHT.cc:832-958
+ *   DHT::handlePutRequest / handleGetRequest          DHT.cc:298-428, 430-497
+ *   DHT::handlePutResponse / handleGetResponse        DHT.cc:553-575, 577-715
+ *   DHT::handleRpcTimeout                             DHT.cc:157-294
+ *   DHTDataStorage::addData / removeData / dumpDht    DHTDataStorage.cc:155-243
+ * An operation is a LookupCall with numSiblings = numReplica (ovs_lookup_batch: an internal RPC, no
+ * delay of its own) and then direct RPCs to the returned siblings.  Each DHTPutCall / DHTGetCall and
+ * each response travels as a BaseAppDataMessage straight over UDP (BaseRpc.cc:173-272,
+ * BaseOverlay.cc:1310-1341, 857-866; BaseApp.cc:572-611): its DHTMessage.msg:30-41 length plus
+ * BASEAPPDATA_L 40 bits plus 28 B UDP/IP, through the sender's transmit queue
+ * (SimpleNodeEntry.cc:164-194), which holds only this operation's own earlier messages; a replica
+ * that is the source itself is reached with no delay (SimpleUDP.cc:320-345).  The RPC timeout is
+ * rpcUdpTimeout (BaseRpc.cc:202-205, retries 0); a response arriving at or after it counts as a
+ * timeout.  measureAuthBlock adds AUTHBLOCK_L to PUTCALL_L and to every response.
+ * A value is a 64-bit token and a length in bytes: the length drives the message sizes, hash equality
+ * is token equality (equal tokens must mean equal values), and the `hashes` map of DHT.cc:602-633 is
+ * ordered UNSPECIFIED_VALUE first, then by ascending token.
+ * Accepted: what ovs_lookup_batch accepts with routingType iterative and lookupParallelRpcs = 1 on an
+ * unsharded Chord or Kademlia network (the source then never has two FindNodeCalls outstanding, so
+ * its transmit queue is idle when the lookup completes).  Everything else is OVS_ENOTSUP, on the host,
+ * before anything is staged; DESIGN.md lists each refusal. */
+#define OVS_HAS_DHT 1
+typedef struct ovs_dht_params {
+    int32_t numReplica;          /* **.tier1*.dht.numReplica = 4 (1..8, <= getMaxNumSiblings()) */
+    int32_t numGetRequests;      /* **.tier1*.dht.numGetRequests = 4 (1..8) */
+    double  ratioIdentical;      /* **.tier1*.dht.ratioIdentical = 0.5 (0 < r <= 1) */
+    int32_t secureMaintenance;   /* must be 0 */
+    int32_t invalidDataAttack;   /* must be 0 */
+    int32_t maintenanceAttack;   /* must be 0 */
+    int32_t pad;                 /* 0 */
+} ovs_dht_params;
+void        ovs_dht_params_default(ovs_dht_params* out);
+/* Overwrite the fields of *p that the .ini text sets through `**.tier1*.dht.*` (default.ini:67-72), and
+ * *test_ttl (may be NULL; seconds) from `**.tier2*.dhtTestApp.testTtl` (default.ini:77); config_name, err
+ * and the file form as ovs_params_from_ini / _file. */
+ovs_status  ovs_dht_params_from_ini(ovs_dht_params* p, int32_t* test_ttl, const char* ini_text,
+                                    const char* config_name, char* err, int err_len);
+ovs_status  ovs_dht_params_from_ini_file(ovs_dht_params* p, int32_t* test_ttl, const char* path,
+                                         const char* config_name, char* err, int err_len);
+
+enum { OVS_DHT_SUCCESS = 0, OVS_DHT_FAILED = 1, OVS_DHT_LOOKUP_FAILED = 2 };
+/* One operation besides its key and source node: put i stores (token, vlen) under (keys[i], kind, id)
+ * with a TTL of ttl seconds (0 = never expires; DHT.cc:410-412); vlen = 0 is a delete.  A get reads
+ * (keys[i], kind, id) and ignores token, vlen and ttl.  t0_ns is the simulation time at which the
+ * DHTputCAPICall / DHTgetCAPICall is handled. */
+typedef struct ovs_dht_op {         /* 32 B */
+    int64_t  t0_ns;
+    uint64_t token;
+    uint32_t kind, id;              /* DHTputCAPICall / DHTgetCAPICall default both to 1 (CommonMessages.msg:412-413) */
+    uint32_t vlen;
+    int32_t  ttl;
+} ovs_dht_op;
+typedef struct ovs_dht_put_out {    /* 24 B */
+    int64_t  latency_ns;            /* DHTputCAPIResponse time - t0; -1 when the lookup failed */
+    uint32_t bytes;                 /* this operation's share of numBytesNormal (calls and responses) */
+    uint16_t hop_count;             /* LookupResponse hopCount ("DHT: Successfuly PUT Hop Count") */
+    uint16_t messages;              /* ... and of normalMessages */
+    uint8_t  outcome;               /* OVS_DHT_* */
+    uint8_t  status;                /* the lookup's OVS_LOOKUP_* */
+    uint8_t  num_sent;              /* PendingRpcsEntry numSent */
+    uint8_t  num_responses;         /* numResponses when the operation completed */
+    uint8_t  pad[4];                /* 0 */
+} ovs_dht_put_out;
+typedef struct ovs_dht_get_out {    /* 40 B */
+    int64_t  latency_ns;
+    uint32_t bytes;
+    uint16_t hop_count;
+    uint16_t messages;
+    uint8_t  outcome, status, num_sent, num_responses;
+    uint32_t result_count;          /* DHTgetCAPIResponse result array size of a successful get: 0 or 1 */
+    uint64_t value_token;
+    uint32_t value_len;
+    uint32_t server;                /* the node whose DHTGetResponse carried the value; 0xFFFFFFFF when none */
+} ovs_dht_get_out;
+typedef struct ovs_dht_entry {      /* 48 B: one DhtDumpEntry */
+    uint32_t key[5];
+    uint32_t kind, id, vlen;
+    uint64_t token;
+    int64_t  expiry_ns;             /* INT64_MAX: never */
+} ovs_dht_entry;
+
+/* The context's data storage: one open-addressing table of `capacity` slots keyed by (node, key, kind,
+ * id), resident on the device.  A slot, once claimed, stays with its entry (a deleted or expired
+ * entry keeps its slot).  create replaces an existing store; loading another network drops it.  DHT
+ * calls on one context must be ordered (one stream, or the caller's own events). */
+ovs_status  ovs_dht_store_create(ovs_ctx* ctx, uint64_t capacity);
+ovs_status  ovs_dht_store_clear(ovs_ctx* ctx);
+/* slots: claimed slots, a high-water mark (deleted and expired entries keep their slot, so it never falls;
+ * ovs_dht_store_clear resets it); refused: put batches that did not fit and changed nothing; collisions
+ * (may be NULL): puts dropped because another entry holds their 64-bit tag (2^-64 per pair of entries).
+ * Synchronises the device. */
+ovs_status  ovs_dht_store_count(ovs_ctx* ctx, uint64_t* slots, uint64_t* refused, uint64_t* collisions);
+/* Batches apply in call order; within a put batch two puts of one entry at one replica are resolved
+ * by (arrival ns, operation index), the later one wins.  A put batch first counts, reading only, the
+ * (operation, replica) pairs whose entry has no slot yet -- an upper bound of the slots it needs: k puts of
+ * one new entry count k times -- so size the store for slots + n * numReplica of the largest batch, not
+ * for the number of entries; when slots + that count > capacity the batch
+ * changes nothing: a host-pointer call returns OVS_ENOMEM, a device-pointer call (which never
+ * synchronises the host) is counted in `refused`.  id = 0 (put) and kind = 0 or id = 0 (get) are
+ * wildcards in the reference (DHT.cc:869-874 draws a random id; DHTDataStorage.cc:199-200, 226-227):
+ * OVS_ENOTSUP in a host-pointer call; a device-pointer call must not pass them.  n < 2^32. */
+ovs_status  ovs_dht_put_batch(ovs_ctx* ctx, const ovs_dht_params* dp, const ovs_key160* keys, const uint32_t* src,
+                              const ovs_dht_op* ops, uint64_t n, ovs_dht_put_out* out, uint32_t flags, void* stream);
+/* A get sees every earlier batch and changes nothing; an entry is absent when its expiry is <= the
+ * DHTGetCall's arrival at that replica. */
+ovs_status  ovs_dht_get_batch(ovs_ctx* ctx, const ovs_dht_params* dp, const ovs_key160* keys, const uint32_t* src,
+                              const ovs_dht_op* ops, uint64_t n, ovs_dht_get_out* out, uint32_t flags, void* stream);
+/* DHTdumpCall (DHT.cc:537-551): node's entries live at now_ns, in insertion order, at most cap of them
+ * into entries (host memory); *count = how many there are.  A diagnostic: each call copies the whole
+ * table (96 B x capacity) to the host. */
+ovs_status  ovs_dht_dump_node(ovs_ctx* ctx, uint32_t node, int64_t now_ns, ovs_dht_entry* entries, uint64_t cap,
+                              uint64_t* count);
+
+/* DHTTestApp statistics (src/tier2/dhttestapp/DHTTestApp.cc:147-234, 439-467) and the DHT's own counters over
+ * one put batch and one get batch.  The caller's GlobalDhtTestMap stays on the host with the caller: for get
+ * i, expect[i] is what findEntry(key) returns when the DHTgetCAPIResponse is handled. */
+typedef struct ovs_dhttest_expect {  /* 24 B */
+    uint64_t token;                  /* DHTEntry value */
+    int64_t  endtime_ns;             /* DHTEntry endtime */
+    uint32_t known;                  /* 0: findEntry() == NULL ("unexpected key", DHTTestApp.cc:194-200) */
+    uint32_t pad;
+} ovs_dhttest_expect;
+typedef struct ovs_dhttest_stats {
+    uint64_t num_put_success, num_put_error;     /* DHTTestApp.cc:161-167 */
+    uint64_t num_get_success, num_get_error;     /* DHTTestApp.cc:185-231 */
+    uint64_t put_latency_sum_ns;                 /* over successful puts (DHTTestApp.cc:163-164) */
+    uint64_t put_latency_sumsq_lo, put_latency_sumsq_hi;   /* sum of ns^2, 128 bits */
+    uint64_t get_latency_sum_ns;                 /* over every get response (DHTTestApp.cc:182-183) */
+    uint64_t get_latency_sumsq_lo, get_latency_sumsq_hi;
+    int64_t  put_latency_min_ns, put_latency_max_ns, get_latency_min_ns, get_latency_max_ns;
+    uint64_t get_latency_count;                  /* gets whose response carries a time (the lookup did not fail) */
+    uint64_t put_hop_count, put_hop_sum;         /* "DHT: Successfuly PUT Hop Count": puts with a valid lookup */
+    uint64_t get_hop_count, get_hop_sum;         /* "DHT: Successfuly GET Hop Count" */
+    uint64_t normal_messages, num_bytes_normal;  /* DHT normalMessages / numBytesNormal, summed over all nodes */
+    ovs_stddev put_latency_s;                    /* "DHTTestApp: PUT Latency (s)" */
+    ovs_stddev get_latency_s;                    /* "DHTTestApp: GET Latency (s)" */
+    ovs_stddev put_success_per_s, put_error_per_s, get_success_per_s, get_error_per_s;   /* finishApp, node order */
+    ovs_stddev get_success_ratio;                /* "DHTTestApp: GET Success Ratio" */
+} ovs_dhttest_stats;
+/* put_out / put_src (n_put) and get_out / get_ops / get_src / expect (n_get) as passed to and returned by the
+ * batch calls; a get whose lookup failed has no response time: it counts as numGetError and in no latency.
+ * Integer sums are reduced on the device; the cStdDevs are finished on the host, the per-node ones in node
+ * order and only for measured_time_s >= 0.1 (GlobalStatistics::MIN_MEASURED).  *stats is host memory. */
+ovs_status  ovs_dhttest_stats_batch(ovs_ctx* ctx, const ovs_dht_put_out* put_out, const uint32_t* put_src, uint64_t n_put,
+                                    const ovs_dht_get_out* get_out, const ovs_dht_op* get_ops, const uint32_t* get_src,
+                                    const ovs_dhttest_expect* expect, uint64_t n_get, double measured_time_s,
+                                    ovs_dhttest_stats* stats, uint32_t flags, void* stream);
+
 /* ---- Chord overlay broadcast (additive to ABI 12; test OVS_HAS_CHORD_BROADCAST) ----
  * Replaces, for a batch of broadcasts on a converged ring (ovs_chord_load):
  *   BroadcastTestApp::initBroadcast / rpcBroadcastRequest  src/tier2/broadcasttestapp/BroadcastTestApp.cc:197-340

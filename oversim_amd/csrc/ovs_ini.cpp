@@ -144,88 +144,92 @@ std::string unquote(const std::string& v)
 
 }  // namespace
 
-extern "C" ovs_status ovs_params_from_ini(ovs_params* p, const char* ini_text, const char* config_name, char* err,
-                                          int err_len)
-{
-    auto set_err = [&](const std::string& m) {
-        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str());
-    };
-    if (!p || !ini_text) { set_err("null argument"); return OVS_EINVAL; }
-    std::map<std::string, Section> secs;
-    std::string cur = "General";
-    secs[cur];
-    // parse (with backslash line continuation)
-    std::string text(ini_text);
-    size_t pos = 0;
-    int lineno = 0;
-    while (pos <= text.size()) {
-        size_t nl = text.find('\n', pos);
-        if (nl == std::string::npos) nl = text.size();
-        std::string line = text.substr(pos, nl - pos);
-        pos = nl + 1;
-        ++lineno;
-        while (!line.empty() && line.back() == '\\' && pos <= text.size()) {
-            size_t nl2 = text.find('\n', pos);
-            if (nl2 == std::string::npos) nl2 = text.size();
-            line = line.substr(0, line.size() - 1) + text.substr(pos, nl2 - pos);
-            pos = nl2 + 1;
-            ++lineno;
-        }
-        // strip comment (not inside quotes)
-        bool inq = false;
-        for (size_t i = 0; i < line.size(); ++i) {
-            if (line[i] == '"') inq = !inq;
-            if (line[i] == '#' && !inq) { line = line.substr(0, i); break; }
-        }
-        line = trim(line);
-        if (line.empty()) continue;
-        if (line.front() == '[') {
-            const size_t e = line.find(']');
-            if (e == std::string::npos) { set_err("bad section header at line " + std::to_string(lineno)); return OVS_EINVAL; }
-            std::string name = trim(line.substr(1, e - 1));
-            if (name.rfind("Config ", 0) == 0) name = trim(name.substr(7));
-            cur = name;
-            secs[cur];
-            continue;
-        }
-        const size_t eq = line.find('=');
-        if (eq == std::string::npos) { set_err("expected key = value at line " + std::to_string(lineno)); return OVS_EINVAL; }
-        const std::string k = trim(line.substr(0, eq)), v = trim(line.substr(eq + 1));
-        if (k == "extends") {
-            size_t a = 0;
-            while (a <= v.size()) {
-                size_t c = v.find(',', a);
-                if (c == std::string::npos) c = v.size();
-                const std::string nm = trim(v.substr(a, c - a));
-                if (!nm.empty()) secs[cur].extends.push_back(nm);
-                a = c + 1;
-            }
-            continue;
-        }
-        secs[cur].entries.push_back({k, v});
-    }
-    // section lookup order
-    std::vector<std::string> order;
-    std::vector<std::string> stack;
-    if (config_name && *config_name && std::strcmp(config_name, "General") != 0) {
-        if (!secs.count(config_name)) { set_err(std::string("no such config: ") + config_name); return OVS_EINVAL; }
-        stack.push_back(config_name);
-    }
-    while (!stack.empty()) {
-        const std::string s = stack.front();
-        stack.erase(stack.begin());
-        bool seen = false;
-        for (auto& o : order) seen |= (o == s);
-        if (seen) continue;
-        if (!secs.count(s)) { set_err("extends unknown config: " + s); return OVS_EINVAL; }
-        order.push_back(s);
-        const auto& ex = secs[s].extends;
-        stack.insert(stack.begin(), ex.begin(), ex.end());
-    }
-    order.push_back("General");
+namespace {
 
-    std::string iter_key;
-    auto lookup = [&](const std::string& path, std::string* val) -> bool {
+// A parsed .ini text: sections, the lookup order of one config, and the first-match lookup
+struct IniDoc {
+    std::map<std::string, Section> secs;
+    std::vector<std::string> order;
+    std::string iter_key;       // a matched key whose value is a parameter study (${...})
+
+    ovs_status parse(const char* ini_text, const char* config_name, std::string* err)
+    {
+        std::string cur = "General";
+        secs[cur];
+        // parse (with backslash line continuation)
+        std::string text(ini_text);
+        size_t pos = 0;
+        int lineno = 0;
+        while (pos <= text.size()) {
+            size_t nl = text.find('\n', pos);
+            if (nl == std::string::npos) nl = text.size();
+            std::string line = text.substr(pos, nl - pos);
+            pos = nl + 1;
+            ++lineno;
+            while (!line.empty() && line.back() == '\\' && pos <= text.size()) {
+                size_t nl2 = text.find('\n', pos);
+                if (nl2 == std::string::npos) nl2 = text.size();
+                line = line.substr(0, line.size() - 1) + text.substr(pos, nl2 - pos);
+                pos = nl2 + 1;
+                ++lineno;
+            }
+            // strip comment (not inside quotes)
+            bool inq = false;
+            for (size_t i = 0; i < line.size(); ++i) {
+                if (line[i] == '"') inq = !inq;
+                if (line[i] == '#' && !inq) { line = line.substr(0, i); break; }
+            }
+            line = trim(line);
+            if (line.empty()) continue;
+            if (line.front() == '[') {
+                const size_t e = line.find(']');
+                if (e == std::string::npos) { *err = "bad section header at line " + std::to_string(lineno); return OVS_EINVAL; }
+                std::string name = trim(line.substr(1, e - 1));
+                if (name.rfind("Config ", 0) == 0) name = trim(name.substr(7));
+                cur = name;
+                secs[cur];
+                continue;
+            }
+            const size_t eq = line.find('=');
+            if (eq == std::string::npos) { *err = "expected key = value at line " + std::to_string(lineno); return OVS_EINVAL; }
+            const std::string k = trim(line.substr(0, eq)), v = trim(line.substr(eq + 1));
+            if (k == "extends") {
+                size_t a = 0;
+                while (a <= v.size()) {
+                    size_t c = v.find(',', a);
+                    if (c == std::string::npos) c = v.size();
+                    const std::string nm = trim(v.substr(a, c - a));
+                    if (!nm.empty()) secs[cur].extends.push_back(nm);
+                    a = c + 1;
+                }
+                continue;
+            }
+            secs[cur].entries.push_back({k, v});
+        }
+        // section lookup order
+        std::vector<std::string> stack;
+        if (config_name && *config_name && std::strcmp(config_name, "General") != 0) {
+            if (!secs.count(config_name)) { *err = std::string("no such config: ") + config_name; return OVS_EINVAL; }
+            stack.push_back(config_name);
+        }
+        while (!stack.empty()) {
+            const std::string s = stack.front();
+            stack.erase(stack.begin());
+            bool seen = false;
+            for (auto& o : order) seen |= (o == s);
+            if (seen) continue;
+            if (!secs.count(s)) { *err = "extends unknown config: " + s; return OVS_EINVAL; }
+            order.push_back(s);
+            const auto& ex = secs[s].extends;
+            stack.insert(stack.begin(), ex.begin(), ex.end());
+        }
+        order.push_back("General");
+
+        return OVS_OK;
+    }
+
+    bool lookup(const std::string& path, std::string* val)
+    {
         for (const auto& sname : order) {
             for (const auto& e : secs[sname].entries) {
                 if (glob(e.key.c_str(), path.c_str())) {
@@ -236,7 +240,26 @@ extern "C" ovs_status ovs_params_from_ini(ovs_params* p, const char* ini_text, c
             }
         }
         return false;
+    }
+};
+
+}  // namespace
+
+extern "C" ovs_status ovs_params_from_ini(ovs_params* p, const char* ini_text, const char* config_name, char* err,
+                                          int err_len)
+{
+    auto set_err = [&](const std::string& m) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str());
     };
+    if (!p || !ini_text) { set_err("null argument"); return OVS_EINVAL; }
+    IniDoc doc;
+    {
+        std::string perr;
+        const ovs_status ps = doc.parse(ini_text, config_name, &perr);
+        if (ps != OVS_OK) { set_err(perr); return ps; }
+    }
+    std::string& iter_key = doc.iter_key;
+    auto lookup = [&](const std::string& path, std::string* val) -> bool { return doc.lookup(path, val); };
 
     const std::string ov = p->overlay == OVS_OVERLAY_KADEMLIA ? "kademlia"
                            : p->overlay == OVS_OVERLAY_KOORDE ? "koorde"
@@ -528,6 +551,57 @@ extern "C" ovs_status ovs_params_from_ini_file(ovs_params* p, const char* path, 
         return OVS_EINVAL;
     }
     return ovs_params_from_ini(p, text.c_str(), config_name, err, err_len);
+}
+
+// **.tier1*.dht.* (default.ini:67-72) and **.tier2*.dhtTestApp.testTtl (default.ini:77) into ovs_dht_params;
+// keys that are absent leave *p as it is.
+extern "C" ovs_status ovs_dht_params_from_ini(ovs_dht_params* p, int32_t* test_ttl, const char* ini_text,
+                                              const char* config_name, char* err, int err_len)
+{
+    auto set_err = [&](const std::string& m) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str());
+    };
+    if (!p || !ini_text) { set_err("null argument"); return OVS_EINVAL; }
+    IniDoc doc;
+    std::string perr, v, bad;
+    const ovs_status ps = doc.parse(ini_text, config_name, &perr);
+    if (ps != OVS_OK) { set_err(perr); return ps; }
+    const std::string host = "SimpleUnderlayNetwork.overlayTerminal[0]";
+    const std::string dht = host + ".tier1.dht.", app = host + ".tier2.dhtTestApp.";
+    if (doc.lookup(dht + "numReplica", &v) && !to_int(unquote(v), &p->numReplica)) bad = "numReplica";
+    if (doc.lookup(dht + "numGetRequests", &v) && !to_int(unquote(v), &p->numGetRequests)) bad = "numGetRequests";
+    if (doc.lookup(dht + "ratioIdentical", &v)) {
+        std::string unit;
+        if (!parse_number(unquote(v), &p->ratioIdentical, &unit) || !unit.empty()) bad = "ratioIdentical";
+    }
+    if (doc.lookup(dht + "secureMaintenance", &v) && !to_bool(unquote(v), &p->secureMaintenance)) bad = "secureMaintenance";
+    if (doc.lookup(dht + "invalidDataAttack", &v) && !to_bool(unquote(v), &p->invalidDataAttack)) bad = "invalidDataAttack";
+    if (doc.lookup(dht + "maintenanceAttack", &v) && !to_bool(unquote(v), &p->maintenanceAttack)) bad = "maintenanceAttack";
+    if (test_ttl && doc.lookup(app + "testTtl", &v)) {
+        double sec = 0;
+        int32_t t = 0;
+        if (to_int(unquote(v), &t)) *test_ttl = t;
+        else if (to_seconds(unquote(v), &sec)) *test_ttl = (int32_t)sec;
+        else bad = "testTtl";
+    }
+    if (!bad.empty()) { set_err("cannot parse dht parameter " + bad); return OVS_EINVAL; }
+    if (!doc.iter_key.empty()) { set_err("parameter studies (${...}) are not supported: " + doc.iter_key); return OVS_ENOTSUP; }
+    return OVS_OK;
+}
+
+extern "C" ovs_status ovs_dht_params_from_ini_file(ovs_dht_params* p, int32_t* test_ttl, const char* path,
+                                                   const char* config_name, char* err, int err_len)
+{
+    if (!p || !path) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "null argument");
+        return OVS_EINVAL;
+    }
+    std::string text, e;
+    if (!read_ini_file(path, 0, &text, &e)) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return OVS_EINVAL;
+    }
+    return ovs_dht_params_from_ini(p, test_ttl, text.c_str(), config_name, err, err_len);
 }
 
 // defaults = the reference's default.ini values (host-only parameter handling, with the binder above)

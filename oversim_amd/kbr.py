@@ -140,6 +140,65 @@ RPC_OUT_DTYPE = np.dtype([("responder", "<u4"), ("hop_count", "<u2"), ("call_hop
                           ("call_latency_ns", "<i8")])
 assert RPC_OUT_DTYPE.itemsize == 32
 RPC_ANSWERED, RPC_TIMEOUT = 0, 1
+DHT_OP_DTYPE = np.dtype([("t0_ns", "<i8"), ("token", "<u8"), ("kind", "<u4"), ("id", "<u4"), ("vlen", "<u4"),
+                         ("ttl", "<i4")])
+assert DHT_OP_DTYPE.itemsize == 32
+DHT_PUT_DTYPE = np.dtype([("latency_ns", "<i8"), ("bytes", "<u4"), ("hop_count", "<u2"), ("messages", "<u2"),
+                          ("outcome", "u1"), ("status", "u1"), ("num_sent", "u1"), ("num_responses", "u1"),
+                          ("pad", "u1", 4)])
+assert DHT_PUT_DTYPE.itemsize == 24
+DHT_GET_DTYPE = np.dtype([("latency_ns", "<i8"), ("bytes", "<u4"), ("hop_count", "<u2"), ("messages", "<u2"),
+                          ("outcome", "u1"), ("status", "u1"), ("num_sent", "u1"), ("num_responses", "u1"),
+                          ("result_count", "<u4"), ("value_token", "<u8"), ("value_len", "<u4"), ("server", "<u4")])
+assert DHT_GET_DTYPE.itemsize == 40
+DHT_ENTRY_DTYPE = np.dtype([("key", "<u4", 5), ("kind", "<u4"), ("id", "<u4"), ("vlen", "<u4"), ("token", "<u8"),
+                            ("expiry_ns", "<i8")])
+assert DHT_ENTRY_DTYPE.itemsize == 48
+DHT_SUCCESS, DHT_FAILED, DHT_LOOKUP_FAILED = 0, 1, 2
+DHT_EXPECT_DTYPE = np.dtype([("token", "<u8"), ("endtime_ns", "<i8"), ("known", "<u4"), ("pad", "<u4")])
+assert DHT_EXPECT_DTYPE.itemsize == 24
+
+
+class DhtParams(C.Structure):
+    """ovs_dht_params: the **.tier1*.dht.* parameters (DHT.cc:65-70)."""
+
+    _fields_ = [("numReplica", C.c_int32), ("numGetRequests", C.c_int32), ("ratioIdentical", C.c_double),
+                ("secureMaintenance", C.c_int32), ("invalidDataAttack", C.c_int32), ("maintenanceAttack", C.c_int32),
+                ("pad", C.c_int32)]
+
+    @classmethod
+    def default(cls) -> "DhtParams":
+        p = cls()
+        lib().ovs_dht_params_default(C.byref(p))
+        return p
+
+    @classmethod
+    def from_ini(cls, ini_text: str, config: str | None = None, base: "DhtParams | None" = None):
+        """(DhtParams, testTtl or None) from .ini text: the `**.tier1*.dht.*` keys and
+        `**.tier2*.dhtTestApp.testTtl`, starting from `base` (default: the defaults)."""
+        return cls._ini(lib().ovs_dht_params_from_ini, ini_text.encode(), config, base)
+
+    @classmethod
+    def from_ini_file(cls, path, config: str | None = None, base: "DhtParams | None" = None):
+        return cls._ini(lib().ovs_dht_params_from_ini_file, str(path).encode(), config, base)
+
+    @classmethod
+    def _ini(cls, fn, arg, config, base):
+        p = base.replace() if base is not None else cls.default()
+        ttl = C.c_int32(-1)
+        err = C.create_string_buffer(512)
+        st = fn(C.byref(p), C.byref(ttl), arg, config.encode() if config else None, err, len(err))
+        if st != 0:
+            raise KbrError(f"ovs_dht_params_from_ini: {STATUS.get(st, st)}: {err.value.decode()}")
+        return p, (ttl.value if ttl.value >= 0 else None)
+
+    def replace(self, **kw) -> "DhtParams":
+        q = DhtParams.from_buffer_copy(self)
+        for k, v in kw.items():
+            if not hasattr(q, k):
+                raise AttributeError(k)
+            setattr(q, k, v)
+        return q
 
 class StdDev(C.Structure):
     """ovs_stddev: one cStdDev summary (GlobalStatistics::addStdDev)."""
@@ -250,6 +309,16 @@ def lib() -> C.CDLL:
         "ovs_kbrtest_lookup_stats_batch": ([vp, vp, vp, i32, vp, vp, u64, C.c_double, i32, C.c_double, vp, u32, vp],
                                            C.c_int),
         "ovs_rpc_batch": ([vp, vp, vp, u64, vp, u32, vp], C.c_int),
+        "ovs_dht_params_default": ([vp], None),
+        "ovs_dht_store_create": ([vp, u64], C.c_int),
+        "ovs_dht_store_clear": ([vp], C.c_int),
+        "ovs_dht_store_count": ([vp, vp, vp, vp], C.c_int),
+        "ovs_dht_params_from_ini": ([vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int], C.c_int),
+        "ovs_dht_params_from_ini_file": ([vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int], C.c_int),
+        "ovs_dhttest_stats_batch": ([vp, vp, vp, u64, vp, vp, vp, vp, u64, C.c_double, vp, u32, vp], C.c_int),
+        "ovs_dht_put_batch": ([vp, vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
+        "ovs_dht_get_batch": ([vp, vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
+        "ovs_dht_dump_node": ([vp, u32, C.c_int64, vp, u64, vp], C.c_int),
         "ovs_kbrtest_rpc_stats_batch": ([vp, vp, vp, vp, u64, C.c_double, i32, C.c_double, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
@@ -343,6 +412,30 @@ class KbrTestRpcStats(C.Structure):
         "dropped_msgs_per_s": "KBRTestApp: RPC Dropped Messages/s",
         "dropped_bytes_per_s": "KBRTestApp: RPC Dropped Bytes/s",
         "delivery_ratio": "KBRTestApp: RPC Delivery Ratio",
+    }
+
+
+class DhtTestStats(C.Structure):
+    """ovs_dhttest_stats: DHTTestApp statistics of a put and a get batch (DHTTestApp.cc:147-234, 439-467)."""
+
+    _fields_ = [
+        ("num_put_success", C.c_uint64), ("num_put_error", C.c_uint64), ("num_get_success", C.c_uint64),
+        ("num_get_error", C.c_uint64), ("put_latency_sum_ns", C.c_uint64), ("put_latency_sumsq_lo", C.c_uint64),
+        ("put_latency_sumsq_hi", C.c_uint64), ("get_latency_sum_ns", C.c_uint64), ("get_latency_sumsq_lo", C.c_uint64),
+        ("get_latency_sumsq_hi", C.c_uint64), ("put_latency_min_ns", C.c_int64), ("put_latency_max_ns", C.c_int64),
+        ("get_latency_min_ns", C.c_int64), ("get_latency_max_ns", C.c_int64), ("get_latency_count", C.c_uint64),
+        ("put_hop_count", C.c_uint64), ("put_hop_sum", C.c_uint64), ("get_hop_count", C.c_uint64),
+        ("get_hop_sum", C.c_uint64), ("normal_messages", C.c_uint64), ("num_bytes_normal", C.c_uint64),
+        ("put_latency_s", StdDev), ("get_latency_s", StdDev), ("put_success_per_s", StdDev),
+        ("put_error_per_s", StdDev), ("get_success_per_s", StdDev), ("get_error_per_s", StdDev),
+        ("get_success_ratio", StdDev),
+    ]
+
+    STDDEV_NAMES = {
+        "put_latency_s": "DHTTestApp: PUT Latency (s)", "get_latency_s": "DHTTestApp: GET Latency (s)",
+        "put_success_per_s": "DHTTestApp: Successful PUT Requests/s", "put_error_per_s": "DHTTestApp: Failed PUT Requests/s",
+        "get_success_per_s": "DHTTestApp: Successful GET Requests/s", "get_error_per_s": "DHTTestApp: Failed GET Requests/s",
+        "get_success_ratio": "DHTTestApp: GET Success Ratio",
     }
 
 
@@ -821,6 +914,83 @@ class KbrEngine:
                                                       float(failureLatency), C.byref(st), 0, None),
                   "ovs_kbrtest_rpc_stats_batch")
         return st
+
+    # -- DHT tier
+    def dht_store_create(self, capacity: int):
+        """The context's DHT data storage: an open-addressing table of `capacity` slots on the device."""
+        self._chk(self._L.ovs_dht_store_create(self._h, int(capacity)), "ovs_dht_store_create")
+
+    def dht_store_clear(self):
+        self._chk(self._L.ovs_dht_store_clear(self._h), "ovs_dht_store_clear")
+
+    def dht_store_count(self) -> tuple[int, int]:
+        """(claimed slots, device-pointer put batches refused for lack of room)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self._L.ovs_dht_store_count(self._h, C.byref(a), C.byref(b), None), "ovs_dht_store_count")
+        return a.value, b.value
+
+    def dhttest_stats(self, put_out, put_src, get_out, get_ops, get_src, expect, measured_time_s: float) -> DhtTestStats:
+        """DHTTestApp statistics of one put batch and one get batch (either may be empty); `expect`
+        (DHT_EXPECT_DTYPE) is the caller's GlobalDhtTestMap entry for each get."""
+        po = np.ascontiguousarray(put_out, dtype=DHT_PUT_DTYPE)
+        ps = np.ascontiguousarray(put_src, dtype=np.uint32)
+        go = np.ascontiguousarray(get_out, dtype=DHT_GET_DTYPE)
+        gp = np.ascontiguousarray(get_ops, dtype=DHT_OP_DTYPE)
+        gs = np.ascontiguousarray(get_src, dtype=np.uint32)
+        ex = np.ascontiguousarray(expect, dtype=DHT_EXPECT_DTYPE)
+        if len(po) != len(ps) or not (len(go) == len(gp) == len(gs) == len(ex)):
+            raise ValueError("records, sources and expectations differ in length")
+        st = DhtTestStats()
+        self._chk(self._L.ovs_dhttest_stats_batch(self._h, _ptr(po), _ptr(ps), len(po), _ptr(go), _ptr(gp), _ptr(gs),
+                                                  _ptr(ex), len(go), float(measured_time_s), C.byref(st), 0, None),
+                  "ovs_dhttest_stats_batch")
+        return st
+
+    def _dht(self, fn, name, dtype, keys, src, ops, dp):
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        ops = np.ascontiguousarray(ops, dtype=DHT_OP_DTYPE)
+        n = len(keys)
+        if not (len(src) == len(ops) == n):
+            raise ValueError("keys, src and ops differ in length")
+        dp = dp if dp is not None else DhtParams.default()
+        out = np.zeros(n, dtype=dtype)
+        self._chk(fn(self._h, C.byref(dp), _ptr(keys), _ptr(src), _ptr(ops), n, _ptr(out), 0, None), name)
+        return out
+
+    def dht_put(self, keys, src, ops, dp: "DhtParams | None" = None) -> np.ndarray:
+        """Batched DHT puts (DHT.cc:499-516, 832-897): put i from node src[i] stores ops[i] (DHT_OP_DTYPE) under
+        keys[i].  Returns DHT_PUT_DTYPE records."""
+        return self._dht(self._L.ovs_dht_put_batch, "ovs_dht_put_batch", DHT_PUT_DTYPE, keys, src, ops, dp)
+
+    def dht_get(self, keys, src, ops, dp: "DhtParams | None" = None) -> np.ndarray:
+        """Batched DHT gets (DHT.cc:518-535, 898-957, 577-715).  Returns DHT_GET_DTYPE records."""
+        return self._dht(self._L.ovs_dht_get_batch, "ovs_dht_get_batch", DHT_GET_DTYPE, keys, src, ops, dp)
+
+    def dht_put_device(self, keys_ptr: int, src_ptr: int, ops_ptr: int, n: int, out_ptr: int,
+                       dp: "DhtParams | None" = None, stream: int | None = None):
+        """Device-resident put batch (async on `stream`; a batch that does not fit is counted by dht_store_count)."""
+        dp = dp if dp is not None else DhtParams.default()
+        self._chk(self._L.ovs_dht_put_batch(self._h, C.byref(dp), C.c_void_p(keys_ptr), C.c_void_p(src_ptr),
+                                            C.c_void_p(ops_ptr), n, C.c_void_p(out_ptr), DEVICE_PTRS,
+                                            C.c_void_p(stream) if stream else None), "ovs_dht_put_batch")
+
+    def dht_get_device(self, keys_ptr: int, src_ptr: int, ops_ptr: int, n: int, out_ptr: int,
+                       dp: "DhtParams | None" = None, stream: int | None = None):
+        dp = dp if dp is not None else DhtParams.default()
+        self._chk(self._L.ovs_dht_get_batch(self._h, C.byref(dp), C.c_void_p(keys_ptr), C.c_void_p(src_ptr),
+                                            C.c_void_p(ops_ptr), n, C.c_void_p(out_ptr), DEVICE_PTRS,
+                                            C.c_void_p(stream) if stream else None), "ovs_dht_get_batch")
+
+    def dht_dump(self, node: int, now_ns: int) -> np.ndarray:
+        """DHTdumpCall: the node's entries live at now_ns in insertion order (DHT_ENTRY_DTYPE)."""
+        cnt = C.c_uint64()
+        self._chk(self._L.ovs_dht_dump_node(self._h, int(node), int(now_ns), None, 0, C.byref(cnt)), "ovs_dht_dump_node")
+        out = np.zeros(cnt.value, dtype=DHT_ENTRY_DTYPE)
+        if cnt.value:
+            self._chk(self._L.ovs_dht_dump_node(self._h, int(node), int(now_ns), _ptr(out), cnt.value, C.byref(cnt)),
+                      "ovs_dht_dump_node")
+        return out
 
     def kbrtest_stats_device(self, out_ptr: int, keys_ptr: int, src_ptr: int, n: int, measured_time_s: float,
                              lookupNodeIds: bool = True, stream: int | None = None) -> KbrTestStats:
