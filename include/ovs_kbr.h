@@ -800,6 +800,79 @@ ovs_status  ovs_chord_broadcast_batch(ovs_ctx* ctx, const uint32_t* initiators, 
                                       int32_t query_bytes, ovs_bcast_node* nodes, ovs_bcast_stats* stats,
                                       uint32_t flags, void* stream);
 
+/* ---- Scribe multicast (additive to ABI 12; test OVS_HAS_SCRIBE) ----
+ * Replaces, on a converged Chord ring (ovs_chord_load) under iterative or semi-recursive routing:
+ *   Scribe::subscribeToGroup / forward / handleJoinMessage / handleJoinResponse   src/applications/scribe/Scribe.cc:113-127, 329-373, 410-431, 459-479
+ *   Scribe::deliverALMDataToRoot / handlePublishCall / deliverALMDataToGroup      Scribe.cc:375-408, 624-704
+ *   BaseApp::handleCommonAPIMessage (forward() before every delivery)             src/common/BaseApp.cc:334-395
+ * in the state "every join answered, no timer fired": no heartbeats, refreshes, leaves or update().
+ * ovs_scribe_build leaves the forest of all groups in the context: the closure of the memberships
+ * under "next hop towards the group key" (semi-recursive: Chord's findNode at every hop; iterative: the
+ * responsible node, a star).  Semi-recursive trees need forward() at intermediate hops, i.e.
+ * useCommonAPIforward = true.  The reference's [Config Scribe] sets that for Pastry only
+ * (omnetpp.ini:309) and default.ini:391 sets it false for other overlays: for Chord it is an assumption
+ * this engine makes, with no parameter to turn it off.  The node responsible for the key absorbs the joins
+ * that reach it like any forwarder and then joins through itself, which makes it the root (parent ==
+ * itself).  A join whose route fails leaves its sender without a parent: an iterative lookup past
+ * hopCountMax; hopCountMax = 0 (dropped at the source); semi-recursive with hopCountMax = 1 when the first
+ * hop is not responsible (sendToKey's hop check precedes forward(), BaseOverlay.cc:1464, 1546).
+ * ovs_scribe_multicast_batch is OVS_ESTATE when routingType or hopCountMax differ from the build's. */
+#define OVS_HAS_SCRIBE 1
+#define OVS_SCRIBE_SUBSCRIBER 1u   /* the node itself subscribed */
+#define OVS_SCRIBE_ROOT       2u   /* parent == the node: it answers publishes */
+#define OVS_SCRIBE_FORWARDER  4u   /* it has children */
+typedef struct ovs_scribe_node {   /* 16 B, one per (group, node) of the forest, sorted by (group, node) */
+    uint32_t group;
+    uint32_t node;
+    uint32_t parent;               /* the node itself at the root; 0xFFFFFFFF: its join was dropped */
+    uint16_t depth;                /* parent steps up to the top of its tree */
+    uint16_t flags;                /* OVS_SCRIBE_* */
+} ovs_scribe_node;
+enum { OVS_SCRIBE_OK = 0, OVS_SCRIBE_WRONG_ROOT = 1, OVS_SCRIBE_ROUTE_FAILED = 2 };
+typedef struct ovs_scribe_msg_out { /* 32 B, one per published message */
+    int64_t  response_ns;          /* the ScribePublishResponse at the sender; -1: the publish route failed */
+    int64_t  last_delivery_ns;     /* latest delivery to a subscriber; -1: none */
+    uint32_t receivers;            /* subscribers the data reached (numReceived) */
+    uint32_t forwarded;            /* copies sent to children (numForward) */
+    uint16_t publish_hops;         /* hops of the ScribePublishCall */
+    uint16_t depth;                /* deepest tree level the data reached */
+    uint8_t  status;               /* OVS_SCRIBE_OK / _WRONG_ROOT / _ROUTE_FAILED */
+    uint8_t  pad[3];
+} ovs_scribe_msg_out;
+typedef struct ovs_scribe_delivery { /* 24 B, one per (message, subscriber reached) */
+    uint32_t msg;
+    uint32_t node;
+    uint32_t hops;                 /* tree hops from the root */
+    uint32_t pad;
+    int64_t  arrival_ns;           /* since the publish was sent */
+} ovs_scribe_delivery;
+/* group_keys[n_groups], member_group[n_members], member_node[n_members] follow `flags`; duplicate
+ * pairs count once.  capacity = the most tree nodes (members and forwarders of all groups) the forest
+ * may hold; one more is OVS_ENOMEM.  Any failure leaves the forest of an earlier call in place.
+ * OVS_ENOTSUP: explicit tables, arcs of a sharded ring, other overlays, full-recursive, exhaustive and
+ * source-routing routing. */
+ovs_status  ovs_scribe_build(ovs_ctx* ctx, const ovs_key160* group_keys, uint64_t n_groups, const uint32_t* member_group,
+                             const uint32_t* member_node, uint64_t n_members, uint64_t capacity, uint32_t flags,
+                             void* stream);
+ovs_status  ovs_scribe_clear(ovs_ctx* ctx);
+/* tree nodes, edges, groups with a root; any pointer may be NULL */
+ovs_status  ovs_scribe_count(ovs_ctx* ctx, uint64_t* nodes, uint64_t* edges, uint64_t* rooted_groups);
+/* out[tree nodes] (ovs_scribe_count) follows `flags` */
+ovs_status  ovs_scribe_export(ovs_ctx* ctx, ovs_scribe_node* out, uint32_t flags, void* stream);
+/* Message i is published by node msg_src[i] to group msg_group[i] at time 0 with payload_bytes of
+ * ALM payload (almTest.messageLength); msg_flags[i] & 1: the sender has cached the rendezvous point
+ * from an earlier ScribePublishResponse and sends straight to it (Scribe.cc:652-654; ignored for a
+ * group without a root, whose "Wrong Root" answers clear the cache).  Messages do not interact.
+ * The root queues its response first, then one copy per child in set order, then delivers locally;
+ * every forwarder does the same without the response.  out[n_msgs] and, if not NULL,
+ * deliveries[deliv_cap] follow `flags`; *deliv_count (host memory, may be NULL) receives the number of
+ * delivery records there are, of which the first deliv_cap are written, in no particular order.  The
+ * level loop runs on the host: the call has completed on `stream` when it returns. */
+ovs_status  ovs_scribe_multicast_batch(ovs_ctx* ctx, const uint32_t* msg_group, const uint32_t* msg_src,
+                                       const uint8_t* msg_flags, uint64_t n_msgs, int32_t payload_bytes,
+                                       ovs_scribe_msg_out* out, ovs_scribe_delivery* deliveries, uint64_t deliv_cap,
+                                       uint64_t* deliv_count, uint32_t flags, void* stream);
+
 /* ---- multi-GPU sharding (one process per GPU; the host exchanges records) ----
  * The sorted ring is cut into contiguous arcs, one per rank.  Node keys,
  * coordinates and 64 B node records are replicated; the finger rows -- the bulk

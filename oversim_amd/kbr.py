@@ -159,6 +159,45 @@ DHT_EXPECT_DTYPE = np.dtype([("token", "<u8"), ("endtime_ns", "<i8"), ("known", 
 assert DHT_EXPECT_DTYPE.itemsize == 24
 
 
+SCRIBE_NODE_DTYPE = np.dtype([("group", "<u4"), ("node", "<u4"), ("parent", "<u4"), ("depth", "<u2"), ("flags", "<u2")])
+SCRIBE_MSG_DTYPE = np.dtype([("response_ns", "<i8"), ("last_delivery_ns", "<i8"), ("receivers", "<u4"),
+                             ("forwarded", "<u4"), ("publish_hops", "<u2"), ("depth", "<u2"), ("status", "u1"),
+                             ("pad", "u1", 3)])
+SCRIBE_DELIVERY_DTYPE = np.dtype([("msg", "<u4"), ("node", "<u4"), ("hops", "<u4"), ("pad", "<u4"), ("arrival_ns", "<i8")])
+SCRIBE_SUBSCRIBER, SCRIBE_ROOT, SCRIBE_FORWARDER = 1, 2, 4
+SCRIBE_STATUS = {0: "OK", 1: "WRONG_ROOT", 2: "ROUTE_FAILED"}
+
+
+class ScribeParams:
+    """What ALMTest sets for a publish: almTest.messageLength (default.ini:81), the ALM payload in bytes."""
+
+    def __init__(self, messageLength: int = 100):
+        self.messageLength = int(messageLength)
+
+    @classmethod
+    def from_ini(cls, text: str, config: str | None = None) -> "ScribeParams":
+        """Reads `**.almTest.messageLength` from ini text: the [General] section, then `config`'s, the
+        last assignment winning; units are not accepted (the key is a plain int)."""
+        out = cls()
+        section = "General"
+        for raw in text.splitlines():
+            line = raw.split("#", 1)[0].strip()
+            if not line:
+                continue
+            if line.startswith("[") and line.endswith("]"):
+                section = line[1:-1].strip()
+                section = section[len("Config "):].strip() if section.startswith("Config ") else section
+                continue
+            if section != "General" and section != config:
+                continue
+            key, sep, val = line.partition("=")
+            if sep and key.strip().endswith("almTest.messageLength"):
+                out.messageLength = int(val.strip())
+        if out.messageLength < 0:
+            raise ValueError("almTest.messageLength must be >= 0")
+        return out
+
+
 class DhtParams(C.Structure):
     """ovs_dht_params: the **.tier1*.dht.* parameters (DHT.cc:65-70)."""
 
@@ -320,6 +359,11 @@ def lib() -> C.CDLL:
         "ovs_dht_get_batch": ([vp, vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
         "ovs_dht_dump_node": ([vp, u32, C.c_int64, vp, u64, vp], C.c_int),
         "ovs_kbrtest_rpc_stats_batch": ([vp, vp, vp, vp, u64, C.c_double, i32, C.c_double, vp, u32, vp], C.c_int),
+        "ovs_scribe_build": ([vp, vp, u64, vp, vp, u64, u64, u32, vp], C.c_int),
+        "ovs_scribe_clear": ([vp], C.c_int),
+        "ovs_scribe_count": ([vp, vp, vp, vp], C.c_int),
+        "ovs_scribe_export": ([vp, vp, u32, vp], C.c_int),
+        "ovs_scribe_multicast_batch": ([vp, vp, vp, vp, u64, i32, vp, vp, u64, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -836,6 +880,80 @@ class KbrEngine:
                                                     C.cast(st, C.c_void_p), DEVICE_PTRS,
                                                     C.c_void_p(stream) if stream else None), "ovs_chord_broadcast_batch")
         return [bcast_stats_dict(st[b]) for b in range(nb)]
+
+    # -- Scribe
+    def scribe_build(self, group_keys, member_group, member_node, capacity: int | None = None):
+        """Build the Scribe forest of all groups (ovs_scribe_build): member_node[i] subscribes to group
+        member_group[i] (an index into group_keys).  capacity = the most tree nodes the forest may hold
+        (default: memberships * 64 + groups, far above a Chord path's length).  Returns (tree nodes,
+        edges, groups with a root)."""
+        gk = keys_array(group_keys) if len(group_keys) else np.zeros((0, 5), np.uint32)
+        mg = np.ascontiguousarray(member_group, dtype=np.uint32)
+        mn = np.ascontiguousarray(member_node, dtype=np.uint32)
+        if len(mg) != len(mn):
+            raise ValueError("member_group and member_node differ in length")
+        if capacity is None:
+            capacity = len(mg) * 64 + len(gk)
+        self._chk(self._L.ovs_scribe_build(self._h, _ptr(gk), len(gk), _ptr(mg), _ptr(mn), len(mg), int(capacity), 0, None),
+                  "ovs_scribe_build")
+        return self.scribe_count()
+
+    def scribe_build_device(self, gk_ptr: int, n_groups: int, mg_ptr: int, mn_ptr: int, n_members: int, capacity: int,
+                            stream: int | None = None):
+        self._chk(self._L.ovs_scribe_build(self._h, C.c_void_p(gk_ptr), n_groups, C.c_void_p(mg_ptr), C.c_void_p(mn_ptr),
+                                           n_members, int(capacity), DEVICE_PTRS, C.c_void_p(stream) if stream else None),
+                  "ovs_scribe_build")
+        return self.scribe_count()
+
+    def scribe_clear(self):
+        self._chk(self._L.ovs_scribe_clear(self._h), "ovs_scribe_clear")
+
+    def scribe_count(self) -> tuple[int, int, int]:
+        a, b, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self._L.ovs_scribe_count(self._h, C.byref(a), C.byref(b), C.byref(r)), "ovs_scribe_count")
+        return a.value, b.value, r.value
+
+    def scribe_export(self) -> np.ndarray:
+        """The forest as SCRIBE_NODE_DTYPE records sorted by (group, node)."""
+        out = np.empty(self.scribe_count()[0], dtype=SCRIBE_NODE_DTYPE)
+        self._chk(self._L.ovs_scribe_export(self._h, _ptr(out), 0, None), "ovs_scribe_export")
+        return out
+
+    def scribe_multicast(self, msg_group, msg_src, known_rp=None, payload_bytes: int = 100, deliveries: bool = True):
+        """Publish message i from node msg_src[i] to group msg_group[i] (ovs_scribe_multicast_batch);
+        known_rp[i]: the sender has the rendezvous point cached.  Returns (out, deliveries): SCRIBE_MSG_DTYPE
+        per message and the SCRIBE_DELIVERY_DTYPE records sorted by (msg, node) (None with deliveries=False)."""
+        mg = np.ascontiguousarray(msg_group, dtype=np.uint32)
+        ms = np.ascontiguousarray(msg_src, dtype=np.uint32)
+        mf = np.zeros(len(mg), np.uint8) if known_rp is None else np.ascontiguousarray(known_rp, dtype=np.uint8)
+        if not (len(mg) == len(ms) == len(mf)):
+            raise ValueError("msg_group, msg_src and known_rp differ in length")
+        out = np.zeros(len(mg), dtype=SCRIBE_MSG_DTYPE)
+        cnt = C.c_uint64()
+        call = lambda d, cap: self._chk(self._L.ovs_scribe_multicast_batch(
+            self._h, _ptr(mg), _ptr(ms), _ptr(mf), len(mg), int(payload_bytes), _ptr(out), _ptr(d), cap, C.byref(cnt), 0,
+            None), "ovs_scribe_multicast_batch")
+        if not deliveries:
+            call(None, 0)
+            return out, None
+        # every subscriber of the message's group at most
+        sub = self.scribe_export()
+        per_group = np.bincount(sub["group"][(sub["flags"] & SCRIBE_SUBSCRIBER) != 0], minlength=1)
+        cap = int(per_group[mg[mg < len(per_group)]].sum()) if len(mg) else 0
+        d = np.zeros(max(cap, 1), dtype=SCRIBE_DELIVERY_DTYPE)
+        call(d, cap)
+        d = d[:min(cnt.value, cap)]
+        return out, d[np.lexsort((d["node"], d["msg"]))]
+
+    def scribe_multicast_device(self, mg_ptr: int, ms_ptr: int, mf_ptr: int, n: int, payload_bytes: int, out_ptr: int,
+                                deliv_ptr: int | None = None, deliv_cap: int = 0, stream: int | None = None) -> int:
+        """The same for device-resident arrays; returns the number of delivery records there are."""
+        cnt = C.c_uint64()
+        self._chk(self._L.ovs_scribe_multicast_batch(
+            self._h, C.c_void_p(mg_ptr), C.c_void_p(ms_ptr), C.c_void_p(mf_ptr), n, int(payload_bytes), C.c_void_p(out_ptr),
+            C.c_void_p(deliv_ptr) if deliv_ptr else None, deliv_cap, C.byref(cnt), DEVICE_PTRS,
+            C.c_void_p(stream) if stream else None), "ovs_scribe_multicast_batch")
+        return cnt.value
 
     def sync(self):
         self._chk(self._L.ovs_sync(self._h), "ovs_sync")
