@@ -1,0 +1,170 @@
+// ctx.hpp -- the context and the host helpers its entry points share (internal).
+//
+// The translation units that implement the C ABI include this: ovs_kbr.cpp (context, loaders, route,
+// lookup, refresh, maintenance, shard steps) and the application tiers app_*.cpp.  The tiers reach the
+// router through route_check / route_device and lookup_check / lookup_device, never through the public
+// entry points: one argument check, one hipSetDevice and one CallFrame per call.  Nothing writes
+// c->P but ovs_set_params and the loaders; a tier that routes under another message length passes a
+// copy.  shard_route.cpp drives a context through the public ABI and sees ctx_internal.hpp only.
+#pragma once
+#include <map>
+#include <vector>
+
+#include "call_frame.hpp"
+#include "ctx_internal.hpp"
+#include "dht.hpp"
+#include "epichord.hpp"
+#include "host_tables.hpp"
+#include "kad.hpp"
+#include "kad_shard.hpp"
+#include "koorde.hpp"
+#include "launch.hpp"
+#include "scribe.hpp"
+
+struct ovs_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    ovs_params P{};
+    int overlay = 0;          // loaded overlay
+    uint64_t n = 0;
+    bool ideal = true;
+    int num_cu = 0;
+    // chord
+    ovs::KeyRec* recs = nullptr;
+    double2* xy = nullptr;
+    ovs::FingerEnt* fingers = nullptr;  // ideal finger rows (64 B entries)
+    uint64_t nfing = 0;
+    ovs::NodeRec* nodes = nullptr;      // ideal node records + finger entries built for successorListSize = nodes_ns
+    ovs::WinRec* win = nullptr;         // ideal successor windows of the arc [shard_lo, shard_hi)
+    int nodes_ns = -1;
+    uint32_t* pred = nullptr;
+    uint32_t* succ = nullptr;
+    uint8_t* nsucc = nullptr;
+    uint32_t* fres = nullptr;
+    int sls = 0;
+    // explicit tables: host copies for batched maintenance (ovs_chord_fix_fingers / _stabilize)
+    ovs::ChordHost ch;
+    // explicit Kademlia tables: host copy for maintenance rounds (ovs_kad_maintenance_round)
+    ovs::KadHost kh;
+    uint64_t shard_lo = 0, shard_hi = 0;   // finger rows exist for [shard_lo, shard_hi)
+    ovs::FingerEnt* ftop = nullptr;         // replicated top finger levels of every node (ovs_chord_shard_replicate)
+    int ftl = 0;
+    uint64_t* d_bounds = nullptr;           // device copy of the arc boundaries (MAXSHARDS + 1)
+    std::vector<uint64_t> h_bounds;         // ... as last uploaded (uploaded again only on a change)
+    std::map<hipStream_t, ovs::StageBuf> stage;  // shard-step stage records per stream (cohorts)
+    bool bbox_ok = false;                   // the coordinates' bounding box (x0, x1, y0, y1), computed
+    double bbox[4] = {0, 0, 0, 0};          // on first use (extendedFingerTable's acceptance rule)
+    // kademlia
+    ovs::KadTables kad{};
+    // koorde (on the sorted ring in recs / xy)
+    ovs::KoordeTables koorde{};
+    // epichord routing snapshot (ovs_epichord_load)
+    ovs::EpiTables epi{};
+    ovs::CachedBuf kvis;                 // internal visited lists (K3 without hop_seq, K2x without responders)
+    // K1's key-order buffers (ksort.hip): sorted keys, sources, caller indices and the sort's
+    // histograms, one allocation shared by the calls on this context like kvis
+    ovs::CachedBuf ks;
+    ovs::CachedBuf bq;                   // the broadcast's item queue (ovs_chord_broadcast_batch), cached like kvis
+    ovs::CachedBuf rpcb;                 // the RPC test's route records and return-route inputs (ovs_rpc_batch)
+    ovs::CachedBuf dhtb;                 // the DHT calls' lookup records, sibling rows and pair arrays (ovs_dht_*_batch)
+    ovs::DhtStore dht;                   // the DHT data storage (ovs_dht_store_create), dropped with the network
+    ovs::ScribeForest scribe;            // the Scribe forest (ovs_scribe_build), dropped with the network
+    ovs::CachedBuf scq;                  // the multicast's item queue (ovs_scribe_multicast_batch), cached like bq
+    ovs::DynSlots dyn;                   // the persistent route kernels' dynamic-tail counters (dyn_acquire)
+    // multi-GPU Kademlia: this rank's in-flight lookups (ovs_kad_shard_begin)
+    void* kst = nullptr;                 // KadLookup<alpha> state records
+    uint8_t* kact = nullptr;             // 0 never runs, 1 suspended in kst, 2 not started
+    ovs::K160* kkeys = nullptr;          // the batch's keys and sources (a lookup starts from them)
+    uint32_t* ksrc = nullptr;
+    uint32_t* kqids = nullptr;
+    void* kres = nullptr;                // alpha findNode result slots per lookup (KadResN<kfcap>)
+    unsigned long long* kbad = nullptr;  // undeliverable responses
+    uint64_t* kiota = nullptr;           // lookup indices 0..n-1: round 1's list, the source of the next lists
+    uint64_t* klist[2] = {nullptr, nullptr};   // ping-pong lists of the still active lookups
+    unsigned long long* knl = nullptr;   // [3]: length of iota (round 1), klist[0], klist[1]
+    int kcur = 0;                        // list of the next round: 0 = iota, 1/2 = klist[0/1]
+    uint64_t knlook = 0, kcap = 0;
+    int kalpha = 0;
+    int kfcap = 8;                       // findNode capacity of the shard records (8; 16 KademliaLarge)
+    int32_t kns = -1;                    // LookupCall batch: numSiblings (-1: KBR routes)
+    uint32_t* ksib = nullptr;            // ... and the caller's sibling rows
+    // the sharded round loop (shard_route.cpp): cohort streams and cached buffers
+    hipStream_t cohort[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* route_scratch = nullptr;
+    void (*route_scratch_release)(void*) = nullptr;
+};
+
+namespace ovs {
+
+// ---- failures as the call's status (fail itself: ctx_internal.hpp) ----
+ovs_status hip_fail(ovs_ctx* c, hipError_t e, const char* where);
+// a CallFrame's or a cached buffer's failure: OVS_ENOMEM when the device is out of memory
+ovs_status device_fail(ovs_ctx* c, hipError_t e, const std::string& what);
+ovs_status frame_fail(ovs_ctx* c, const CallFrame& F);
+ovs_status lease_fail(ovs_ctx* c, const char* name, const CachedBuf::Lease& L);
+
+#define HIPCHK(c, expr)                                             \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return ovs::hip_fail((c), e_, #expr); \
+    } while (0)
+
+// ---- the parameters as the kernels take them ----
+// SimTime(double) on the host (identical IEEE double arithmetic to the device path)
+int64_t simtime_host(double seconds, int round);
+int32_t route_bytes(const ovs_params& P);
+DelayConsts delay_consts(const ovs_params& P);
+
+// ---- refusals ----
+ovs_status check_common(ovs_ctx* c, const ovs_params& P);
+ovs_status check_chord_route(ovs_ctx* c, const ovs_params& P);
+// host-pointer calls: every lookup's source must be a node of the network (a source past it would
+// be read out of bounds by the lookup kernels); device-pointer calls leave that to the caller (ovs_kbr.h)
+ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev);
+
+// ---- the loaded ring ----
+// NodeRec array of an ideal ring for the context's successorListSize (rebuilt when it changes)
+ovs_status ensure_nodes(ovs_ctx* c, hipStream_t s);
+ChordView chord_view(const ovs_ctx* c);
+
+inline uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
+
+// ---- the route seam ----
+// P is the context's parameters, or a copy that differs in what one call sets (the message length, the
+// number of siblings); the tables (ensure_nodes, chord_view) always follow the context's.
+//
+// route_check: every refusal of a one-way route that does not depend on the batch, in ovs_route_batch's
+// order; selects the device and brings an ideal ring's node records up to date on s.
+ovs_status route_check(ovs_ctx* c, const ovs_params& P, hipStream_t s);
+// route_device: n > 0 routes on device pointers, queued on s, after route_check and check_sources.
+// dhop: the caller's hop rows (n * max(hopCountMax, 1)) or nullptr, drpc: its RPC counts or nullptr;
+// F is the call's frame (exhaustive-iterative Kademlia takes a temporary from it).
+ovs_status route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
+                        ovs_route_out* dout, uint32_t* dhop, uint32_t* drpc, hipStream_t s);
+// The same for LookupCalls.  lookup_check resolves num_siblings (< 0: the overlay's maximum) into *ns;
+// dsib has max(ns, 1) entries per lookup.
+ovs_status lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_siblings, hipStream_t s, int32_t* ns);
+ovs_status lookup_device(ovs_ctx* c, const ovs_params& P, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
+                         ovs_route_out* dout, uint32_t* dsib, hipStream_t s);
+
+// ---- read-backs ----
+// the control words of a frontier loop (queue length, error bits, ...), read after the launches queued on s
+inline hipError_t read_ctl(unsigned long long* h, const unsigned long long* ctl, int words, hipStream_t s)
+{
+    const hipError_t e = hipMemcpyAsync(h, ctl, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, s);
+    return e == hipSuccess ? hipStreamSynchronize(s) : e;
+}
+
+// What the statistics calls (ovs_kbrtest_*_stats_batch, ovs_dhttest_stats_batch) share.  stats_begin: the
+// refusals that do not depend on the records, the device, the pointer mode and the stream.
+// stats_read: after the launch (its error in `launched`), the kernel's sums and its second result (per-node
+// counters or reductions) read back; it synchronises s in both pointer modes: the results are host values.
+ovs_status stats_begin(ovs_ctx* c, double measured_time_s, double failure_latency_s, uint32_t flags, void* stream,
+                       bool* dev, hipStream_t* s);
+ovs_status stats_read(ovs_ctx* c, hipStream_t s, hipError_t launched, void* sums, const void* dsums, size_t sums_bytes,
+                      void* rows, const void* drows, size_t rows_bytes, const char* what);
+// rows * c->n zeroed host counters for stats_read
+ovs_status node_counters(ovs_ctx* c, int rows, std::vector<uint32_t>& nc);
+
+}  // namespace ovs

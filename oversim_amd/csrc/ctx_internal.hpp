@@ -1,5 +1,6 @@
-// ctx_internal.hpp -- what the host layers outside ovs_kbr.cpp may use of a context (internal).
+// ctx_internal.hpp -- what a host layer that does not see inside a context may use of it (internal).
 //
+// The translation units that implement the ABI see the context itself (ctx.hpp, which includes this).
 // The sharded round loop (shard_route.cpp) drives a context through the public ABI; these give it
 // the context's device, its error slot, cohort streams the context owns (the shard step keeps its
 // stage records per stream, so the streams must live as long as the context) and one cached
@@ -14,7 +15,8 @@
 namespace ovs {
 
 int ctx_device(const ovs_ctx* c);
-ovs_status ctx_fail(ovs_ctx* c, ovs_status s, const std::string& msg);
+// the call's status; the message is what ovs_last_error returns
+ovs_status fail(ovs_ctx* c, ovs_status s, const std::string& msg);
 // cohort stream i (0..3) of the context, created non-blocking on first use
 hipStream_t ctx_cohort_stream(ovs_ctx* c, int i);
 // the context's slot for the round loop's cached buffers, released with `release` at destroy

@@ -6,6 +6,11 @@
 // call_frame.hpp), run on the context's stream and are synchronous;
 // OVS_DEVICE_PTRS calls launch asynchronously on the caller's stream.  No C++
 // exception crosses the boundary.
+//
+// Here: the context (ctx.hpp), the loaders, the route, lookup, refresh and maintenance entry points and
+// the shard steps, and the helpers ctx.hpp declares.  The application tiers stacked on the route and
+// lookup seam (route_check / route_device, lookup_check / lookup_device) are app_kbrtest.cpp,
+// app_dht.cpp, app_bcast.cpp and app_scribe.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,107 +18,19 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <type_traits>
-#include <vector>
 
-#include "call_frame.hpp"
-#include "chord_bcast.hpp"
-#include "ctx_internal.hpp"
-#include "epichord.hpp"
-#include "dht.hpp"
-#include "host_tables.hpp"
-#include "kad.hpp"
-#include "kad_shard.hpp"
-#include "kbr_rpc.hpp"
-#include "koorde.hpp"
-#include "launch.hpp"
+#include "ctx.hpp"
 #include "persist.hpp"
-#include "scribe.hpp"
-#include "stats.hpp"
 
 using namespace ovs;
-
-struct ovs_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    ovs_params P{};
-    int overlay = 0;          // loaded overlay
-    uint64_t n = 0;
-    bool ideal = true;
-    int num_cu = 0;
-    // chord
-    KeyRec* recs = nullptr;
-    double2* xy = nullptr;
-    FingerEnt* fingers = nullptr;  // ideal finger rows (64 B entries)
-    uint64_t nfing = 0;
-    NodeRec* nodes = nullptr;      // ideal node records + finger entries built for successorListSize = nodes_ns
-    WinRec* win = nullptr;         // ideal successor windows of the arc [shard_lo, shard_hi)
-    int nodes_ns = -1;
-    uint32_t* pred = nullptr;
-    uint32_t* succ = nullptr;
-    uint8_t* nsucc = nullptr;
-    uint32_t* fres = nullptr;
-    int sls = 0;
-    // explicit tables: host copies for batched maintenance (ovs_chord_fix_fingers / _stabilize)
-    ChordHost ch;
-    // explicit Kademlia tables: host copy for maintenance rounds (ovs_kad_maintenance_round)
-    KadHost kh;
-    uint64_t shard_lo = 0, shard_hi = 0;   // finger rows exist for [shard_lo, shard_hi)
-    FingerEnt* ftop = nullptr;              // replicated top finger levels of every node (ovs_chord_shard_replicate)
-    int ftl = 0;
-    uint64_t* d_bounds = nullptr;           // device copy of the arc boundaries (MAXSHARDS + 1)
-    std::vector<uint64_t> h_bounds;         // ... as last uploaded (uploaded again only on a change)
-    std::map<hipStream_t, StageBuf> stage;  // shard-step stage records per stream (cohorts)
-    bool bbox_ok = false;                   // the coordinates' bounding box (x0, x1, y0, y1), computed
-    double bbox[4] = {0, 0, 0, 0};          // on first use (extendedFingerTable's acceptance rule)
-    // kademlia
-    KadTables kad{};
-    // koorde (on the sorted ring in recs / xy)
-    KoordeTables koorde{};
-    // epichord routing snapshot (ovs_epichord_load)
-    EpiTables epi{};
-    CachedBuf kvis;                      // internal visited lists (K3 without hop_seq, K2x without responders)
-    // K1's key-order buffers (ksort.hip): sorted keys, sources, caller indices and the sort's
-    // histograms, one allocation shared by the calls on this context like kvis
-    CachedBuf ks;
-    CachedBuf bq;                        // the broadcast's item queue (ovs_chord_broadcast_batch), cached like kvis
-    CachedBuf rpcb;                      // the RPC test's route records and return-route inputs (ovs_rpc_batch)
-    CachedBuf dhtb;                      // the DHT calls' lookup records, sibling rows and pair arrays (ovs_dht_*_batch)
-    DhtStore dht;                        // the DHT data storage (ovs_dht_store_create), dropped with the network
-    ScribeForest scribe;                 // the Scribe forest (ovs_scribe_build), dropped with the network
-    CachedBuf scq;                       // the multicast's item queue (ovs_scribe_multicast_batch), cached like bq
-    DynSlots dyn;                        // the persistent route kernels' dynamic-tail counters (dyn_acquire)
-    // multi-GPU Kademlia: this rank's in-flight lookups (ovs_kad_shard_begin)
-    void* kst = nullptr;                 // KadLookup<alpha> state records
-    uint8_t* kact = nullptr;             // 0 never runs, 1 suspended in kst, 2 not started
-    K160* kkeys = nullptr;               // the batch's keys and sources (a lookup starts from them)
-    uint32_t* ksrc = nullptr;
-    uint32_t* kqids = nullptr;
-    void* kres = nullptr;                // alpha findNode result slots per lookup (KadResN<kfcap>)
-    unsigned long long* kbad = nullptr;  // undeliverable responses
-    uint64_t* kiota = nullptr;           // lookup indices 0..n-1: round 1's list, the source of the next lists
-    uint64_t* klist[2] = {nullptr, nullptr};   // ping-pong lists of the still active lookups
-    unsigned long long* knl = nullptr;   // [3]: length of iota (round 1), klist[0], klist[1]
-    int kcur = 0;                        // list of the next round: 0 = iota, 1/2 = klist[0/1]
-    uint64_t knlook = 0, kcap = 0;
-    int kalpha = 0;
-    int kfcap = 8;                       // findNode capacity of the shard records (8; 16 KademliaLarge)
-    int32_t kns = -1;                    // LookupCall batch: numSiblings (-1: KBR routes)
-    uint32_t* ksib = nullptr;            // ... and the caller's sibling rows
-    // the sharded round loop (shard_route.cpp): cohort streams and cached buffers
-    hipStream_t cohort[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* route_scratch = nullptr;
-    void (*route_scratch_release)(void*) = nullptr;
-};
 
 namespace ovs {
 
 int ctx_device(const ovs_ctx* c) { return c->device; }
 
-ovs_status ctx_fail(ovs_ctx* c, ovs_status s, const std::string& msg)
+ovs_status fail(ovs_ctx* c, ovs_status s, const std::string& msg)
 {
     if (c) c->err = msg;
     return s;
@@ -135,17 +52,7 @@ void ctx_set_route_scratch(ovs_ctx* c, void* p, void (*release)(void*))
     c->route_scratch_release = release;
 }
 
-}  // namespace ovs
-
-namespace {
-
-ovs_status fail(ovs_ctx* c, ovs_status s, const std::string& m)
-{
-    if (c) c->err = m;
-    return s;
-}
-
-bool fault_injected(const char* what)
+static bool fault_injected(const char* what)
 {
     const char* f = std::getenv("OVS_FAULT_INJECT");
     return f && std::strcmp(f, what) == 0;
@@ -156,13 +63,7 @@ ovs_status hip_fail(ovs_ctx* c, hipError_t e, const char* where)
     return fail(c, OVS_EDEVICE, std::string(where) + ": " + hipGetErrorString(e));
 }
 
-#define HIPCHK(c, expr)                                        \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return hip_fail((c), e_, #expr); \
-    } while (0)
-
-void free_tables(ovs_ctx* c)
+static void free_tables(ovs_ctx* c)
 {
     void* ptrs[] = {c->recs, c->xy, c->fingers, c->pred, c->succ, c->nsucc, c->fres, c->nodes, c->win, c->ftop};
     for (void* p : ptrs)
@@ -190,7 +91,7 @@ void free_tables(ovs_ctx* c)
     c->kh.clear();
 }
 
-void free_kad_shard(ovs_ctx* c)
+static void free_kad_shard(ovs_ctx* c)
 {
     void* ptrs[] = {c->kst, c->kact, c->kqids, c->kres, c->kbad, c->kiota, c->klist[0], c->klist[1], c->knl,
                     c->kkeys, c->ksrc};
@@ -205,7 +106,7 @@ void free_kad_shard(ovs_ctx* c)
 // A zeroed work counter for one launch of a persistent route kernel (the dynamic tail of K1,
 // launch_chord_route, and K2, kad_route), released when the lease goes out of scope: get() is
 // nullptr when none can be had -- the kernel then runs static slices only.
-DynSlots::Lease dyn_acquire(ovs_ctx* c, uint64_t n, hipStream_t s)
+static DynSlots::Lease dyn_acquire(ovs_ctx* c, uint64_t n, hipStream_t s)
 {
     if (!persist_dyn_enabled()) return {};                // A/B: static slices only
     if (n < (1ull << 18)) return {};                      // small batches: static slices (no memset, no event)
@@ -228,7 +129,7 @@ ovs_status lease_fail(ovs_ctx* c, const char* name, const CachedBuf::Lease& L)
 // K1 key order, opt-in (OVS_K1_SORT=1): one-way iterative Chord batches of at least
 // OVS_K1_SORT_MIN lookups (default 2^20) routed in the order of their keys' top bits.  Off by default:
 // measured, the sort costs more than the locality it buys at any bin width one pass can sort
-bool ksort_wanted(uint64_t n)
+static bool ksort_wanted(uint64_t n)
 {
     const char* o = std::getenv("OVS_K1_SORT");      // read per call (one getenv per batch)
     const int on = o ? std::atoi(o) : 0;
@@ -321,7 +222,7 @@ ovs_status check_common(ovs_ctx* c, const ovs_params& P)
 
 // coordDelay of the farthest pair the bounding box admits (host copy of engine.hpp coord_ns: the
 // same IEEE operations; every step is monotone in |dx|, |dy|, so no pair of nodes exceeds it)
-int64_t coord_ns_host(double dx, double dy, int round)
+static int64_t coord_ns_host(double dx, double dy, int round)
 {
     const double s2 = dx * dx + dy * dy;
     const float f = (float)std::sqrt(s2);
@@ -336,7 +237,7 @@ int64_t coord_ns_host(double dx, double dy, int round)
 // next candidate).  Accepted when no call can: the largest RTT the coordinates' bounding box admits
 // (call + the largest response + twice the farthest coordinate delay) is below rpcUdpTimeout
 // (the oracle restates the candidates, tests/test_oracle_extended.py).
-ovs_status check_extended_fingers(ovs_ctx* c, const ovs_params& P)
+static ovs_status check_extended_fingers(ovs_ctx* c, const ovs_params& P)
 {
     if (!c->ideal)
         return fail(c, OVS_ENOTSUP, "extendedFingerTable: explicit tables carry no finger candidate lists");
@@ -426,7 +327,7 @@ ovs_status ensure_nodes(ovs_ctx* c, hipStream_t s)
 }
 
 // upload sorted ids (+ coordinates) into KeyRec / double2 arrays
-ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const double* xy, bool dev)
+static ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const double* xy, bool dev)
 {
     if (n < 2) return fail(c, OVS_EINVAL, "need at least 2 nodes");
     if (n >= 0xFFFFFFFFull) return fail(c, OVS_EINVAL, "too many nodes for 32-bit node indices");
@@ -454,7 +355,7 @@ ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const dou
     return OVS_OK;
 }
 
-}  // namespace
+}  // namespace ovs
 
 // ===========================================================================
 extern "C" {
@@ -1479,9 +1380,10 @@ ovs_status ovs_epichord_find_node_batch(ovs_ctx* c, const uint32_t* node, const 
     return OVS_OK;
 }
 
-// host-pointer calls: every lookup's source must be a node of the network (a source past it would
-// be read out of bounds by the lookup kernels); device-pointer calls leave that to the caller (ovs_kbr.h)
-static ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev)
+extern "C++" {
+namespace ovs {
+
+ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev)
 {
     if (dev) return OVS_OK;
     for (uint64_t i = 0; i < n; ++i)
@@ -1489,82 +1391,75 @@ static ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, boo
     return OVS_OK;
 }
 
-ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n,
-                           ovs_route_out* out, uint32_t* hop_seq, uint32_t* rpcs, uint32_t flags, void* stream)
+ovs_status route_check(ovs_ctx* c, const ovs_params& P, hipStream_t s)
 {
-    if (!c || (!keys && n) || (!src && n) || (!out && n)) return OVS_EINVAL;
     if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
     if (c->overlay == OVS_OVERLAY_EPICHORD)
         return fail(c, OVS_ENOTSUP, "EpiChord lookups rewrite the caches they route over (DESIGN.md §9): "
                                     "ovs_epichord_find_node_batch only");
-    ovs_status st = check_common(c, c->P);
+    ovs_status st = check_common(c, P);
     if (st != OVS_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;   // NULL = the default stream
-    const int H = c->P.hopCountMax > 0 ? c->P.hopCountMax : 1;
     if (c->overlay == OVS_OVERLAY_CHORD) {
-        st = check_chord_route(c, c->P);
+        st = check_chord_route(c, P);
         if (st != OVS_OK) return st;
         if (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n))
             return fail(c, OVS_ESTATE, "context holds one arc of a sharded ring: use ovs_shard_step");
         // explicit tables: the hop list (hopCountMax entries) is the lookup's visited set
-        if (!c->ideal && c->P.hopCountMax < 1)
+        if (!c->ideal && P.hopCountMax < 1)
             return fail(c, OVS_ENOTSUP, "explicit Chord tables need hopCountMax >= 1 (the hop list is the visited set)");
-        st = ensure_nodes(c, s);
-        if (st != OVS_OK) return st;
-    } else if (c->overlay == OVS_OVERLAY_KOORDE) {
-        if (c->P.routingType != 0) return fail(c, OVS_ENOTSUP, "Koorde routing is implemented for routingType = iterative");
+        return ensure_nodes(c, s);
+    }
+    if (c->overlay == OVS_OVERLAY_KOORDE) {
+        if (P.routingType != 0) return fail(c, OVS_ENOTSUP, "Koorde routing is implemented for routingType = iterative");
         // the hop list (hopCountMax entries) is the visitOnlyOnce list: no hop limit leaves it without a size
-        if (c->P.hopCountMax < 1) return fail(c, OVS_ENOTSUP, "Koorde lookups need hopCountMax >= 1");
-        if (c->P.lookupRedundantNodes != 1 || c->P.lookupParallelRpcs != 1 || c->P.lookupMerge ||
-            c->P.numSiblings != 1 || !c->P.lookupVisitOnlyOnce)
+        if (P.hopCountMax < 1) return fail(c, OVS_ENOTSUP, "Koorde lookups need hopCountMax >= 1");
+        if (P.lookupRedundantNodes != 1 || P.lookupParallelRpcs != 1 || P.lookupMerge || P.numSiblings != 1 ||
+            !P.lookupVisitOnlyOnce)
             return fail(c, OVS_ENOTSUP,
                         "Koorde route kernel implements lookupRedundantNodes=1, lookupParallelRpcs=1, merge off, "
                         "visitOnlyOnce, numSiblings=1 (the Koorde defaults)");
-    } else if (c->P.routingType < 0 || c->P.routingType > 4) {
+        return OVS_OK;
+    }
+    if (P.routingType < 0 || P.routingType > 4)
         return fail(c, OVS_ENOTSUP, "Kademlia routing is implemented for routingType = iterative / semi-recursive / "
                                     "full-recursive / exhaustive-iterative / source-routing-recursive");
-    } else if (c->kad.general && c->P.routingType == 3) {
+    if (c->kad.general && P.routingType == 3)
         return fail(c, OVS_ENOTSUP, "CSR (b > 1 / nr128 / nkademlia) tables: routingType iterative or recursive");
-    } else if (c->P.numSiblings != 1) {
+    if (P.numSiblings != 1)
         return fail(c, OVS_ENOTSUP, "the one-way route implements numSiblings = 1 (LookupCall: ovs_lookup_batch)");
-    } else if (c->kad.lo != 0 || c->kad.hi != c->n) {
+    if (c->kad.lo != 0 || c->kad.hi != c->n)
         return fail(c, OVS_ESTATE, "context holds one arc of a sharded network: use ovs_kad_shard_step");
-    }
-    if (n == 0) return OVS_OK;
-    st = check_sources(c, src, n, dev);
-    if (st != OVS_OK) return st;
-    CallFrame F(dev, s);
-    CachedBuf::Lease vis;
-    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
-    const uint32_t* ds = F.in(src, n);
-    ovs_route_out* dout = F.out(out, n);
+    return OVS_OK;
+}
+
+ovs_status route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
+                        ovs_route_out* dout, uint32_t* dhop, uint32_t* drpc, hipStream_t s)
+{
+    const int H = P.hopCountMax > 0 ? P.hopCountMax : 1;
+    const bool hop_seq = dhop != nullptr;
     // hop sequence buffer: always needed for explicit Chord tables and Koorde (the visited check).
     // Koorde without a hop_seq request uses a context scratch buffer, unpadded: K3 reads back only
     // the entries a lookup wrote
     const bool koorde_scratch = c->overlay == OVS_OVERLAY_KOORDE && !hop_seq;
     // exhaustive-iterative Kademlia: the responder list is the lookup's visited set
-    const bool kad_exh = c->overlay == OVS_OVERLAY_KADEMLIA && c->P.routingType == 3;
+    const bool kad_exh = c->overlay == OVS_OVERLAY_KADEMLIA && P.routingType == 3;
     // source-routing-recursive Kademlia: the hop list is the message's visitedHops
-    const bool kad_src = c->overlay == OVS_OVERLAY_KADEMLIA && c->P.routingType == 4;
+    const bool kad_src = c->overlay == OVS_OVERLAY_KADEMLIA && P.routingType == 4;
     const bool need_hop = hop_seq || (c->overlay == OVS_OVERLAY_CHORD && !c->ideal) || kad_exh || kad_src;
-    uint32_t* dhop = nullptr;
-    if (hop_seq) {
-        dhop = F.out(hop_seq, n * (uint64_t)H);
-    } else if (koorde_scratch || need_hop) {
+    CachedBuf::Lease vis;
+    if (!hop_seq && (koorde_scratch || need_hop)) {
         // an internal hop list (Koorde, explicit Chord tables, exhaustive Kademlia: the visited sets) in
         // the context's cached buffer, not a per-call allocation
         vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
         if (!vis) return lease_fail(c, "kvis", vis);
         dhop = reinterpret_cast<uint32_t*>(vis.data());
     }
-    uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
-    if (!F.ok()) return frame_fail(c, F);
     if (dhop && !koorde_scratch) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+    const DelayConsts DC = delay_consts(P);
     hipError_t e;
     if (c->overlay == OVS_OVERLAY_CHORD) {
-        LookupConsts LC{c->P.hopCountMax, c->P.numSiblings, c->P.lookupRedundantNodes, c->P.routingType != 0};
+        LookupConsts LC{P.hopCountMax, P.numSiblings, P.lookupRedundantNodes, P.routingType != 0};
         if (c->ideal && !LC.recursive && ksort_wanted(n)) {
             // key order: the batch sorted by its keys' top bits, results written at the caller's indices, in
             // the context's key-order buffers: the sort's scratch, caller indices, sorted sources and keys
@@ -1576,13 +1471,10 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
             K160* sk = reinterpret_cast<K160*>(ss + n);
             const char* kb = std::getenv("OVS_K1_SORT_BITS");
             e = ksort_launch(dk, ds, n, scr, sk, ss, pm, kb ? std::atoi(kb) : 14, s);
-            if (e == hipSuccess)
-                e = launch_chord_route(chord_view(c), c->ideal, delay_consts(c->P), LC, sk, ss, n, dout, dhop, c->num_cu,
-                                       s, pm);
+            if (e == hipSuccess) e = launch_chord_route(chord_view(c), c->ideal, DC, LC, sk, ss, n, dout, dhop, c->num_cu, s, pm);
         } else {
             const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-            e = launch_chord_route(chord_view(c), c->ideal, delay_consts(c->P), LC, dk, ds, n, dout, dhop, c->num_cu, s,
-                                   nullptr, dyn.get());
+            e = launch_chord_route(chord_view(c), c->ideal, DC, LC, dk, ds, n, dout, dhop, c->num_cu, s, nullptr, dyn.get());
         }
         if (e == hipSuccess && drpc) {
             if (LC.recursive) e = hipMemsetAsync(drpc, 0, sizeof(uint32_t) * n, s);   // no FindNodeCalls
@@ -1590,8 +1482,8 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
         }
     } else if (c->overlay == OVS_OVERLAY_KOORDE) {
         const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-        e = koorde_route(c->koorde, c->recs, c->xy, delay_consts(c->P), c->P.hopCountMax, dk, ds, n, dout, dhop,
-                         !koorde_scratch, drpc, c->num_cu, s, dyn.get());
+        e = koorde_route(c->koorde, c->recs, c->xy, DC, P.hopCountMax, dk, ds, n, dout, dhop, !koorde_scratch, drpc,
+                         c->num_cu, s, dyn.get());
     } else if (kad_exh) {
         // sendToKey with EXHAUSTIVE_ITERATIVE_ROUTING (BaseOverlay.cc:1434-1442): lookup(key, numSiblings = 1)
         // with redundantNodes = lookupRedundantNodes, the route message to getResult()[0]
@@ -1599,34 +1491,28 @@ ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* s
         if (!F.ok()) return frame_fail(c, F);
         bool cap_err = false;
         // dhop was filled with NONE above: the kernel leaves the rows unpadded
-        e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), c->P.lookupRedundantNodes, 1, true,
-                           dk, ds, n, dout, dres, dhop, nullptr, drpc, c->num_cu, s, persist_dyn_enabled(), &cap_err, nullptr, false,
-                           hop_seq == nullptr /* nobody reads the visited sets: their first entries in LDS */);
+        e = kad_exhaustive(c->kad, c->xy, (uint32_t)c->n, P, DC, P.lookupRedundantNodes, 1, true, dk, ds, n, dout, dres, dhop,
+                           nullptr, drpc, c->num_cu, s, persist_dyn_enabled(), &cap_err, nullptr, false,
+                           !hop_seq /* nobody reads the visited sets: their first entries in LDS */);
         if (e == hipSuccess && cap_err) return fail(c, OVS_ENOTSUP, "a lookup exceeded the kernel's capacity (64 timed-out nodes)");
-    } else if (c->P.routingType == 1 || c->P.routingType == 2 || kad_src) {
+    } else if (P.routingType == 1 || P.routingType == 2 || kad_src) {
         // R/Kademlia: recursive routing with Kademlia's recursiveRoutingHook (kad_general.hip)
-        e = kad_route_recursive(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P),
-                                simtime_host(c->P.rpcKeyTimeout, c->P.simtimeRound), 1, dk, ds, n, dout, dhop, nullptr, s);
+        e = kad_route_recursive(c->kad, c->xy, (uint32_t)c->n, P, DC, simtime_host(P.rpcKeyTimeout, P.simtimeRound), 1, dk, ds,
+                                n, dout, dhop, nullptr, s);
         if (e == hipSuccess && drpc) e = hipMemsetAsync(drpc, 0, sizeof(uint32_t) * n, s);   // no FindNodeCalls
     } else if (c->kad.general) {
-        e = kad_route_general(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), dk, ds, n, dout, dhop, drpc, s,
-                              nullptr);
+        e = kad_route_general(c->kad, c->xy, (uint32_t)c->n, P, DC, dk, ds, n, dout, dhop, drpc, s, nullptr);
     } else {
         const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-        e = kad_route(c->kad, c->xy, (uint32_t)c->n, c->P, delay_consts(c->P), dk, ds, n, dout, dhop, drpc,
-                      c->num_cu, s, nullptr, dyn.get());
+        e = kad_route(c->kad, c->xy, (uint32_t)c->n, P, DC, dk, ds, n, dout, dhop, drpc, c->num_cu, s, nullptr, dyn.get());
     }
-    vis.release();
+    vis.release();      // dhop is ordered by the buffer's event: a device-pointer call stays asynchronous
     if (e != hipSuccess) return hip_fail(c, e, "route kernel");
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
 
-ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, int32_t num_siblings,
-                            ovs_lookup_out* out, uint32_t* siblings, uint32_t flags, void* stream)
+ovs_status lookup_check(ovs_ctx* c, const ovs_params& P0, int32_t num_siblings, hipStream_t s, int32_t* ns_out)
 {
-    static_assert(sizeof(ovs_lookup_out) == sizeof(ovs_route_out), "lookup results are finished in place");
-    if (!c || (n && (!keys || !src || !out || !siblings))) return OVS_EINVAL;
     if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
     if (c->overlay == OVS_OVERLAY_KOORDE)
         return fail(c, OVS_ENOTSUP, "Koorde: ovs_route_batch and ovs_koorde_find_node_batch only");
@@ -1635,18 +1521,18 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
     const bool chord = c->overlay == OVS_OVERLAY_CHORD;
     // BaseOverlay::lookupRpc: numSiblings < 0 -> getMaxNumSiblings() (Chord.cc getMaxNumSiblings =
     // successorListSize, Kademlia.cc:347-350 = s); isSiblingFor rejects larger values
-    const int32_t maxs = chord ? c->P.successorListSize : c->P.s;
+    const int32_t maxs = chord ? P0.successorListSize : P0.s;
     const int32_t ns = num_siblings < 0 ? maxs : num_siblings;
     if (ns > maxs) return fail(c, OVS_EINVAL, "numSiblings too big!");
-    if (ns == 0 && c->P.routingType == 3)
+    if (ns == 0 && P0.routingType == 3)
         return fail(c, OVS_ENOTSUP, "LookupCall with numSiblings = 0 (exact-key lookup): iterative or recursive routing");
-    if (ns == 0 && chord && c->P.routingType != 0)
+    if (ns == 0 && chord && P0.routingType != 0)
         return fail(c, OVS_ENOTSUP, "Chord LookupCall with numSiblings = 0 (exact-key lookup): iterative routing");
-    if (ns == 0 && chord && c->P.hopCountMax < 1)
+    if (ns == 0 && chord && P0.hopCountMax < 1)
         return fail(c, OVS_ENOTSUP, "Chord exact-key LookupCalls need hopCountMax >= 1");
     if (ns > 8) return fail(c, OVS_ENOTSUP, "LookupCall implements numSiblings <= 8");
-    ovs_params P = c->P;
-    P.numSiblings = 1;          // the route checks: one-way configuration, numSiblings applied below
+    ovs_params P = P0;
+    P.numSiblings = 1;          // the route checks: one-way configuration, numSiblings applied by lookup_device
     ovs_status st = check_common(c, P);
     if (st != OVS_OK) return st;
     const bool kad_exh = !chord && P.routingType == 3;
@@ -1659,8 +1545,7 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
     if (kad_exh && ns > P.lookupRedundantNodes)
         return fail(c, OVS_EINVAL, "With EXHAUSTIVE_ITERATIVE_ROUTING numRedundantNodes must be >= numSiblings!");
     HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    *ns_out = ns;
     if (chord) {
         st = check_chord_route(c, P);
         if (st != OVS_OK) return st;
@@ -1668,15 +1553,21 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
             return fail(c, OVS_ESTATE, "context holds one arc of a sharded ring: LookupCall needs the whole ring");
         if (!c->ideal && P.hopCountMax < 1)
             return fail(c, OVS_ENOTSUP, "explicit Chord tables need hopCountMax >= 1 (the hop list is the visited set)");
-        st = ensure_nodes(c, s);
-        if (st != OVS_OK) return st;
-    } else if (c->kad.lo != 0 || c->kad.hi != c->n) {
-        return fail(c, OVS_ESTATE, "context holds one arc of a sharded network: LookupCall needs the whole network");
+        return ensure_nodes(c, s);
     }
-    if (n == 0) return OVS_OK;
-    st = check_sources(c, src, n, dev);
-    if (st != OVS_OK) return st;
+    if (c->kad.lo != 0 || c->kad.hi != c->n)
+        return fail(c, OVS_ESTATE, "context holds one arc of a sharded network: LookupCall needs the whole network");
+    return OVS_OK;
+}
+
+ovs_status lookup_device(ovs_ctx* c, const ovs_params& P0, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
+                         ovs_route_out* dout, uint32_t* dsib, hipStream_t s)
+{
+    const bool chord = c->overlay == OVS_OVERLAY_CHORD;
+    ovs_params P = P0;
     P.numSiblings = ns;
+    const bool kad_exh = !chord && P.routingType == 3;
+    const bool kad_rec = !chord && (P.routingType == 1 || P.routingType == 2 || P.routingType == 4);
     const int nslots = ns ? ns : 1;      // an exact-key lookup keeps a one-slot sibling vector (IterativeLookup.cc:149)
     DelayConsts DC = delay_consts(P);
     DC.lookupCall = 1;
@@ -1687,13 +1578,7 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
         DC.msgRespSib = 2 * simtime_host((double)((int64_t)(DC.respBase + DC.respPerNode * nodes) * 8) / P.datarate,
                                          P.simtimeRound) + DC.access2;
     }
-    CallFrame F(dev, s);
     CachedBuf::Lease vis;
-    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
-    const uint32_t* ds = F.in(src, n);
-    ovs_route_out* dout = F.out(reinterpret_cast<ovs_route_out*>(out), n);
-    uint32_t* dsib = F.out(siblings, n * (uint64_t)nslots);
-    if (!F.ok()) return frame_fail(c, F);
     uint32_t* dhop = nullptr;
     // Chord exact-key lookups replay the one-way chain recorded one hop beyond hopCountMax
     const bool chord_exact = chord && ns == 0;
@@ -1744,6 +1629,58 @@ ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* 
     if (e == hipSuccess && !kad_exh) e = launch_lookup_finish(chord_view(c), chord, c->ideal, nslots, dout, dsib, n, s);
     vis.release();      // dhop is ordered by the buffer's event: a device-pointer call stays asynchronous
     if (e != hipSuccess) return hip_fail(c, e, "lookup kernel");
+    return OVS_OK;
+}
+
+}  // namespace ovs
+}  // extern "C++"
+
+ovs_status ovs_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                           ovs_route_out* out, uint32_t* hop_seq, uint32_t* rpcs, uint32_t flags, void* stream)
+{
+    if (!c || (!keys && n) || (!src && n) || (!out && n)) return OVS_EINVAL;
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;   // NULL = the default stream
+    ovs_status st = route_check(c, c->P, s);
+    if (st != OVS_OK) return st;
+    if (n == 0) return OVS_OK;
+    st = check_sources(c, src, n, dev);
+    if (st != OVS_OK) return st;
+    const int H = c->P.hopCountMax > 0 ? c->P.hopCountMax : 1;
+    CallFrame F(dev, s);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dout = F.out(out, n);
+    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * (uint64_t)H) : nullptr;
+    uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
+    st = route_device(c, c->P, F, dk, ds, n, dout, dhop, drpc, s);
+    if (st != OVS_OK) return st;
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
+    return OVS_OK;
+}
+
+ovs_status ovs_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, int32_t num_siblings,
+                            ovs_lookup_out* out, uint32_t* siblings, uint32_t flags, void* stream)
+{
+    static_assert(sizeof(ovs_lookup_out) == sizeof(ovs_route_out), "lookup results are finished in place");
+    if (!c || (n && (!keys || !src || !out || !siblings))) return OVS_EINVAL;
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    int32_t ns = 0;
+    ovs_status st = lookup_check(c, c->P, num_siblings, s, &ns);
+    if (st != OVS_OK) return st;
+    if (n == 0) return OVS_OK;
+    st = check_sources(c, src, n, dev);
+    if (st != OVS_OK) return st;
+    CallFrame F(dev, s);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dout = F.out(reinterpret_cast<ovs_route_out*>(out), n);
+    uint32_t* dsib = F.out(siblings, n * (uint64_t)(ns ? ns : 1));
+    if (!F.ok()) return frame_fail(c, F);
+    st = lookup_device(c, c->P, ns, dk, ds, n, dout, dsib, s);
+    if (st != OVS_OK) return st;
     if (F.finish() != hipSuccess) return frame_fail(c, F);
     return OVS_OK;
 }
@@ -2115,1058 +2052,6 @@ ovs_status ovs_delay_batch(ovs_ctx* c, const uint32_t* a, const uint32_t* b, con
     hipError_t e = launch_delay(c->xy, delay_consts(c->P), da, db, dbytes, n, dout, s);
     if (e != hipSuccess) return hip_fail(c, e, "delay kernel");
     if (F.finish() != hipSuccess) return frame_fail(c, F);
-    return OVS_OK;
-}
-
-extern "C++" {
-namespace {
-
-// The statistics kernels over one staged batch: the scratch they reduce in, the launch, and the sums
-// (h) and per-node reductions (r, NSTAT rows of sum, sum of squares, min, max, count) read back.
-// The read-back synchronises the stream in both pointer modes: the results are host values.
-ovs_status run_stats(ovs_ctx* c, CallFrame& F, hipStream_t s, const ovs_route_out* dout, const K160* dk, const uint32_t* ds,
-                     uint64_t n, int32_t lookup_node_ids, double measured_time_s, uint64_t msg_bytes, const uint32_t* dsib,
-                     uint64_t sib_stride, StatsDev* h, double* r)
-{
-    StatsDev* S = F.scratch<StatsDev>(1);
-    uint32_t* counts = F.scratch<uint32_t>(3 * c->n);
-    double* partial = F.scratch<double>(STATS_NODE_BLOCKS * NSTAT * 5);
-    double* result = F.scratch<double>(NSTAT * 5);
-    if (!F.ok()) return frame_fail(c, F);
-    // GlobalStatistics::MIN_MEASURED = 0.1 s (GlobalStatistics.cc:32, KBRTestApp.cc:502)
-    const int rates = measured_time_s >= 0.1;
-    hipError_t e = launch_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids, measured_time_s, msg_bytes,
-                                rates, S, counts, partial, result, c->num_cu, s, dsib, sib_stride);
-    if (e == hipSuccess) e = hipMemcpyAsync(h, S, sizeof *h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(r, result, sizeof(double) * NSTAT * 5, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(c, e, "statistics kernels");
-    return OVS_OK;
-}
-
-// cStdDev::getMean / getVariance (OMNeT++ 4.x) of row k of run_stats' reductions: sample variance, 0
-// below two values or if negative
-void finish_stddev(const double* r, int k, ovs_stddev& d)
-{
-    const double sum = r[k * 5 + 0], sq = r[k * 5 + 1];
-    uint64_t cnt;
-    std::memcpy(&cnt, &r[k * 5 + 4], sizeof cnt);
-    d.count = cnt;
-    if (!cnt) return;
-    d.mean = sum / (double)cnt;
-    double var = 0.0;
-    if (cnt > 1) {
-        var = (sq - sum * sum / (double)cnt) / (double)(cnt - 1);
-        if (var < 0) var = 0;
-    }
-    d.stddev = std::sqrt(var);
-    d.min = r[k * 5 + 2];
-    d.max = r[k * 5 + 3];
-}
-
-}  // namespace
-}  // extern "C++"
-
-ovs_status ovs_kbrtest_stats_batch(ovs_ctx* c, const ovs_route_out* out, const ovs_key160* keys, const uint32_t* src,
-                                   uint64_t n, double measured_time_s, int32_t lookup_node_ids,
-                                   ovs_kbrtest_stats* stats, uint32_t flags, void* stream)
-{
-    if (!c || !stats || (n && (!out || !src || (lookup_node_ids && !keys)))) return OVS_EINVAL;
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (!(measured_time_s >= 0)) return fail(c, OVS_EINVAL, "measured_time_s must be >= 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;   // NULL = the default stream
-    CallFrame F(dev || n == 0, s);                            // an empty batch has nothing to stage
-    const ovs_route_out* dout = F.in(out, n);
-    const uint32_t* ds = F.in(src, n);
-    const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
-    StatsDev h{};
-    double r[NSTAT * 5];
-    const ovs_status st = run_stats(c, F, s, dout, dk, ds, n, lookup_node_ids, measured_time_s,
-                                    (uint64_t)c->P.testMsgSize, nullptr, 0, &h, r);
-    if (st != OVS_OK) return st;
-
-    ovs_kbrtest_stats& o = *stats;
-    std::memset(&o, 0, sizeof o);
-    const uint64_t B = (uint64_t)c->P.testMsgSize;
-    o.num_sent = n;
-    o.num_delivered = h.delivered;
-    o.num_dropped = h.dropped;
-    o.num_lookup_failed = h.failed;
-    o.bytes_sent = n * B;
-    o.bytes_delivered = h.delivered * B;
-    o.bytes_dropped = h.dropped * B;
-    o.hop_count_sum = h.hop_sum;
-    o.latency_sum_ns = (int64_t)h.lat_sum;
-    if (h.delivered) {
-        o.hop_count_min = (uint32_t)h.hop_min;
-        o.hop_count_max = (uint32_t)h.hop_max;
-        o.latency_min_ns = (int64_t)h.lat_min;
-        o.latency_max_ns = (int64_t)h.lat_max;
-        // GlobalStatistics::finalizeStatistics: OutVector value / count (GlobalStatistics.cc:134-139);
-        // latency values are SIMTIME_DBL(latency), summed here exactly in ns
-        o.hop_count_mean = (double)h.hop_sum / (double)h.delivered;
-        o.latency_mean_s = ((double)h.lat_sum / (double)h.delivered) * 1e-9;
-    }
-    for (int i = 0; i < 8; ++i) o.status_count[i] = h.status[i];
-    for (int i = 0; i < 64; ++i) o.hop_hist[i] = h.hist[i];
-    ovs_stddev* sd[NSTAT] = {&o.delivered_msgs_per_s, &o.delivered_bytes_per_s, &o.dropped_msgs_per_s,
-                             &o.dropped_bytes_per_s, &o.delivery_ratio};
-    for (int k = 0; k < NSTAT; ++k) finish_stddev(r, k, *sd[k]);
-    return OVS_OK;
-}
-
-ovs_status ovs_kbrtest_lookup_stats_batch(ovs_ctx* c, const ovs_lookup_out* out, const uint32_t* siblings,
-                                          int32_t siblings_stride, const ovs_key160* keys, const uint32_t* src,
-                                          uint64_t n, double measured_time_s, int32_t lookup_node_ids,
-                                          double failure_latency_s, ovs_kbrtest_lookup_stats* stats, uint32_t flags,
-                                          void* stream)
-{
-    if (!c || !stats || siblings_stride < 1 || (n && (!out || !src || !siblings || (lookup_node_ids && !keys))))
-        return OVS_EINVAL;
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (!(measured_time_s >= 0)) return fail(c, OVS_EINVAL, "measured_time_s must be >= 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    CallFrame F(dev || n == 0, s);                            // an empty batch has nothing to stage
-    const ovs_route_out* dout = F.in(reinterpret_cast<const ovs_route_out*>(out), n);
-    const uint32_t* ds = F.in(src, n);
-    const uint32_t* dsib = F.in(siblings, n * (uint64_t)siblings_stride);
-    const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
-    StatsDev h{};
-    double r[NSTAT * 5];
-    const ovs_status st = run_stats(c, F, s, dout, dk, ds, n, lookup_node_ids, measured_time_s, 0, dsib ? dsib : src,
-                                    (uint64_t)siblings_stride, &h, r);
-    if (st != OVS_OK) return st;
-
-    ovs_kbrtest_lookup_stats& o = *stats;
-    std::memset(&o, 0, sizeof o);
-    o.num_sent = n;
-    o.num_success = h.delivered;
-    o.num_failed = h.dropped;
-    o.num_invalid = h.failed;
-    o.hop_count_sum = h.hop_sum;
-    o.failed_hop_count_sum = h.fhop_sum;
-    o.success_latency_sum_ns = (int64_t)h.lat_sum;
-    if (h.delivered) {
-        o.hop_count_min = (uint32_t)h.hop_min;
-        o.hop_count_max = (uint32_t)h.hop_max;
-        o.success_latency_min_ns = (int64_t)h.lat_min;
-        o.success_latency_max_ns = (int64_t)h.lat_max;
-        o.hop_count_mean = (double)h.hop_sum / (double)h.delivered;
-        o.success_latency_mean_s = ((double)h.lat_sum / (double)h.delivered) * 1e-9;
-    }
-    if (h.dropped) o.failed_hop_count_mean = (double)h.fhop_sum / (double)h.dropped;
-    if (n) o.total_latency_mean_s = ((double)h.lat_sum * 1e-9 + (double)h.dropped * failure_latency_s) / (double)n;
-    for (int i = 0; i < 8; ++i) o.status_count[i] = h.status[i];
-    for (int i = 0; i < 64; ++i) o.hop_hist[i] = h.hist[i];
-    finish_stddev(r, 0, o.successful_lookups_per_s);
-    finish_stddev(r, 2, o.failed_lookups_per_s);
-    finish_stddev(r, 4, o.success_ratio);
-    return OVS_OK;
-}
-
-// KBRTestApp RPC test (KBRTestApp.cc:172-189, 230-329): the call leg is ovs_route_batch itself, on this
-// call's staged copies, so its checks and messages are inherited; k_rpc_finish adds the response leg and
-// the timeout rule; full-recursive routing routes the responses back (BaseApp.cc:595-599) and folds them
-// in.  Everything is queued on one stream with no host synchronisation in between.
-ovs_status ovs_rpc_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_rpc_out* out,
-                         uint32_t flags, void* stream)
-{
-    static_assert(sizeof(ovs_rpc_out) == 32, "ovs_rpc_out is 32 B");
-    if (!c || (!keys && n) || (!src && n) || (!out && n)) return OVS_EINVAL;
-    // the route's own refusals (no network, EpiChord, an arc of a sharded network, parameters), before
-    // anything is staged: an empty batch runs exactly its checks
-    ovs_status st = ovs_route_batch(c, keys, src, 0, nullptr, nullptr, nullptr, flags, stream);
-    if (st != OVS_OK) return st;
-    if (c->P.routingType == 4)
-        return fail(c, OVS_ENOTSUP, "KbrTestCall under source-routing-recursive routing: the response follows the "
-                                    "call's recorded hops back (BaseRpc.cc:576-584), which is not implemented");
-    if (c->P.routingType < 0 || c->P.routingType > 2)
-        return fail(c, OVS_ENOTSUP, "KbrTestCall is implemented for routingType iterative / semi-recursive / full-recursive");
-    if (!(c->P.rpcKeyTimeout >= 0)) return fail(c, OVS_EINVAL, "rpcKeyTimeout must be >= 0");
-    if (n == 0) return OVS_OK;
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    st = check_sources(c, src, n, dev);
-    if (st != OVS_OK) return st;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    const bool full = c->P.routingType == 2;
-    CallFrame F(dev, s);
-    const ovs_key160* dk = F.in(keys, n);
-    const uint32_t* ds = F.in(src, n);
-    ovs_rpc_out* dout = F.out(out, n);
-    if (!F.ok()) return frame_fail(c, F);
-    // route records (16 B), and for the return route its keys (20 B) and sources (4 B), each part 256 B aligned
-    const uint64_t o_keys = (sizeof(ovs_route_out) * n + 255) & ~255ull;
-    const uint64_t o_src = o_keys + ((sizeof(K160) * n + 255) & ~255ull);
-    CachedBuf::Lease buf = c->rpcb.acquire(full ? o_src + sizeof(uint32_t) * n : o_keys, s);
-    if (!buf) return lease_fail(c, "RPC buffers", buf);
-    ovs_route_out* droute = reinterpret_cast<ovs_route_out*>(buf.data());
-    K160* rkeys = full ? reinterpret_cast<K160*>(buf.data() + o_keys) : nullptr;
-    uint32_t* rsrc = full ? reinterpret_cast<uint32_t*>(buf.data() + o_src) : nullptr;
-    st = ovs_route_batch(c, dk, ds, n, droute, nullptr, nullptr, OVS_DEVICE_PTRS, s);
-    if (st != OVS_OK) return st;
-    RpcConsts RC{};
-    const DelayConsts DC = delay_consts(c->P);
-    RC.timeout = simtime_host(c->P.rpcKeyTimeout, c->P.simtimeRound);
-    // KbrTestResponse in a BaseAppDataMessage straight over UDP: payload + BASEAPPDATA_L 40 bits + UDP/IP 28 B
-    // (BaseOverlay.cc:1340-1341, CommonMessages.msg:68, SimpleUDP.cc:291)
-    RC.respMsg = 2 * simtime_host((double)((int64_t)(c->P.testMsgSize + 5 + 28) * 8) / c->P.datarate, c->P.simtimeRound) +
-                 DC.access2;
-    RC.round = c->P.simtimeRound;
-    RC.full = full;
-    RC.nnodes = (uint32_t)c->n;
-    hipError_t e = launch_rpc_finish(droute, ds, c->recs, c->xy, RC, n, dout, rkeys, rsrc, c->num_cu, s);
-    if (e != hipSuccess) return hip_fail(c, e, "RPC finish kernel");
-    if (full) {
-        // the return routes overwrite the call routes: what the fold needs of those is in dout
-        st = ovs_route_batch(c, reinterpret_cast<const ovs_key160*>(rkeys), rsrc, n, droute, nullptr, nullptr,
-                             OVS_DEVICE_PTRS, s);
-        if (st != OVS_OK) return st;
-        e = launch_rpc_fold(droute, ds, RC, n, dout, c->num_cu, s);
-        if (e != hipSuccess) return hip_fail(c, e, "RPC fold kernel");
-    }
-    buf.release();
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    return OVS_OK;
-}
-
-ovs_status ovs_kbrtest_rpc_stats_batch(ovs_ctx* c, const ovs_rpc_out* out, const ovs_key160* keys, const uint32_t* src,
-                                       uint64_t n, double measured_time_s, int32_t lookup_node_ids,
-                                       double failure_latency_s, ovs_kbrtest_rpc_stats* stats, uint32_t flags,
-                                       void* stream)
-{
-    if (!c || !stats || (n && (!out || !src || (lookup_node_ids && !keys)))) return OVS_EINVAL;
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (!(measured_time_s >= 0)) return fail(c, OVS_EINVAL, "measured_time_s must be >= 0");
-    if (!(failure_latency_s >= 0)) return fail(c, OVS_EINVAL, "failure_latency_s must be >= 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    CallFrame F(dev || n == 0, s);                            // an empty batch has nothing to stage
-    const ovs_rpc_out* dout = F.in(out, n);
-    const uint32_t* ds = F.in(src, n);
-    const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
-    RpcStatsDev* S = F.scratch<RpcStatsDev>(1);
-    uint32_t* counts = F.scratch<uint32_t>(3 * c->n);
-    if (!F.ok()) return frame_fail(c, F);
-    RpcStatsDev h{};
-    std::vector<uint32_t> nc;
-    try {
-        nc.resize(3 * c->n);
-    } catch (const std::bad_alloc&) {
-        return fail(c, OVS_ENOMEM, "per-node counters");
-    }
-    hipError_t e = launch_rpc_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids, S, counts, c->num_cu, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(nc.data(), counts, sizeof(uint32_t) * nc.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(c, e, "RPC statistics kernel");
-
-    ovs_kbrtest_rpc_stats& o = *stats;
-    std::memset(&o, 0, sizeof o);
-    const uint64_t B = (uint64_t)c->P.testMsgSize;
-    o.num_sent = n;
-    o.num_delivered = h.delivered;
-    o.num_dropped = h.dropped;
-    o.num_timeout = h.timeout;
-    o.bytes_sent = n * B;
-    o.bytes_delivered = h.delivered * B;
-    o.bytes_dropped = h.dropped * B;
-    o.hop_count_sum = h.hop_sum;
-    o.success_latency_sum_ns = (int64_t)h.lat_sum;
-    if (h.delivered) {
-        o.hop_count_min = (uint32_t)h.hop_min;
-        o.hop_count_max = (uint32_t)h.hop_max;
-        o.success_latency_min_ns = (int64_t)h.lat_min;
-        o.success_latency_max_ns = (int64_t)h.lat_max;
-        o.hop_count_mean = (double)h.hop_sum / (double)h.delivered;
-        o.success_latency_mean_s = ((double)h.lat_sum / (double)h.delivered) * 1e-9;
-    }
-    // "RPC Total Latency": rtt for delivered RPCs, failureLatency for the others (KBRTestApp.cc:262-263, 281-285, 306-310)
-    if (n) o.total_latency_mean_s = ((double)h.lat_sum * 1e-9 + (double)h.dropped * failure_latency_s) / (double)n;
-    for (int i = 0; i < 8; ++i) o.status_count[i] = h.status[i];
-    for (int i = 0; i < 64; ++i) o.hop_hist[i] = h.hist[i];
-    // KBRTestApp::finishApp (KBRTestApp.cc:519-545) at every node, in node order: cStdDev::collect
-    // (count, sum, sum of squares, min, max); only from GlobalStatistics::MIN_MEASURED = 0.1 s on (502)
-    if (measured_time_s >= 0.1) {
-        double r[NSTAT * 5];
-        uint64_t cnt[NSTAT] = {0, 0, 0, 0, 0};
-        for (int k = 0; k < NSTAT; ++k) {
-            r[k * 5 + 0] = 0; r[k * 5 + 1] = 0; r[k * 5 + 2] = INFINITY; r[k * 5 + 3] = -INFINITY;
-        }
-        auto add = [&](int k, double v) {
-            r[k * 5 + 0] += v;
-            r[k * 5 + 1] += v * v;
-            if (v < r[k * 5 + 2]) r[k * 5 + 2] = v;
-            if (v > r[k * 5 + 3]) r[k * 5 + 3] = v;
-            ++cnt[k];
-        };
-        const uint64_t N = c->n;
-        for (uint64_t v = 0; v < N; ++v) {
-            const uint32_t sent = nc[v], d = nc[N + v], dr = nc[2 * N + v];
-            add(0, (double)d / measured_time_s);
-            add(1, (double)((uint64_t)d * B) / measured_time_s);
-            add(2, (double)dr / measured_time_s);
-            add(3, (double)((uint64_t)dr * B) / measured_time_s);
-            if (sent > 0) add(4, (double)((float)d / (float)sent));
-        }
-        for (int k = 0; k < NSTAT; ++k) std::memcpy(&r[k * 5 + 4], &cnt[k], sizeof(uint64_t));
-        ovs_stddev* sd[NSTAT] = {&o.delivered_msgs_per_s, &o.delivered_bytes_per_s, &o.dropped_msgs_per_s,
-                                 &o.dropped_bytes_per_s, &o.delivery_ratio};
-        for (int k = 0; k < NSTAT; ++k) finish_stddev(r, k, *sd[k]);
-    }
-    return OVS_OK;
-}
-
-// ---- DHT tier (DHT.cc): the lookup phase is ovs_lookup_batch on this call's staged copies; dht.hip adds
-// the replica phase and owns the storage.  Every refusal below happens before anything is staged.
-void ovs_dht_params_default(ovs_dht_params* out)
-{
-    if (!out) return;
-    std::memset(out, 0, sizeof *out);
-    out->numReplica = 4;         // default.ini: **.tier*.dht.numReplica = 4
-    out->numGetRequests = 4;
-    out->ratioIdentical = 0.5;
-}
-
-namespace {
-
-ovs_status dht_check(ovs_ctx* c, const ovs_dht_params* dp)
-{
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (c->overlay == OVS_OVERLAY_KOORDE)
-        return fail(c, OVS_ENOTSUP, "DHT on Koorde: LookupCalls (ovs_lookup_batch) are not implemented for Koorde");
-    if (c->overlay == OVS_OVERLAY_EPICHORD)
-        return fail(c, OVS_ENOTSUP, "DHT on EpiChord: LookupCalls (ovs_lookup_batch) are not implemented for EpiChord");
-    const bool chord = c->overlay == OVS_OVERLAY_CHORD;
-    if (chord ? (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n)) : (c->kad.lo != 0 || c->kad.hi != c->n))
-        return fail(c, OVS_ENOTSUP, "DHT on a shard context: the storage and the LookupCall need the whole network on one device");
-    if (c->P.routingType != 0)
-        return fail(c, OVS_ENOTSUP, "DHT with a recursive or exhaustive routingType: the lookup's messages are not the "
-                                    "source's own, so its transmit queue at lookup completion is not modelled; iterative only");
-    if (c->P.lookupParallelRpcs > 1)
-        return fail(c, OVS_ENOTSUP, "DHT with lookupParallelRpcs > 1: the source's transmit queue could still hold "
-                                    "FindNodeCalls when the lookup completes");
-    if (dp->secureMaintenance) return fail(c, OVS_ENOTSUP, "dht.secureMaintenance: sibling votes are not implemented");
-    if (dp->invalidDataAttack) return fail(c, OVS_ENOTSUP, "dht.invalidDataAttack: malicious nodes are not implemented");
-    if (dp->maintenanceAttack) return fail(c, OVS_ENOTSUP, "dht.maintenanceAttack: malicious nodes are not implemented");
-    if (dp->numReplica < 1 || dp->numReplica > DHT_MAXR)
-        return fail(c, OVS_ENOTSUP, "dht.numReplica outside 1..8");
-    if (dp->numGetRequests < 1 || dp->numGetRequests > DHT_MAXR)
-        return fail(c, OVS_ENOTSUP, "dht.numGetRequests outside 1..8");
-    if (!(dp->ratioIdentical > 0 && dp->ratioIdentical <= 1))
-        return fail(c, OVS_ENOTSUP, "dht.ratioIdentical outside (0, 1]: a get could wait for ever with no hash chosen");
-    // DHT.cc:84-87: "numReplica bigger than what this overlay can handle"
-    if (dp->numReplica > (chord ? c->P.successorListSize : c->P.s))
-        return fail(c, OVS_ENOTSUP, "dht.numReplica > getMaxNumSiblings()");
-    if (!c->dht.slots) return fail(c, OVS_ESTATE, "no DHT store: ovs_dht_store_create first");
-    // the LookupCall's own refusals: an empty batch runs exactly its checks
-    return ovs_lookup_batch(c, nullptr, nullptr, 0, dp->numReplica, nullptr, nullptr, 0, nullptr);
-}
-
-DhtConsts dht_consts(const ovs_ctx* c, const ovs_dht_params* dp)
-{
-    DhtConsts C{};
-    C.timeout = simtime_host(c->P.rpcUdpTimeout, c->P.simtimeRound);
-    C.access = simtime_host(c->P.accessDelay, c->P.simtimeRound);
-    C.datarate = c->P.datarate;
-    C.ratio = dp->ratioIdentical;
-    C.round = c->P.simtimeRound;
-    C.auth = c->P.measureAuthBlock ? 800 : 0;      // AUTHBLOCK_L (CommonMessages.msg:45-47, 57)
-    C.R = dp->numReplica;
-    C.G = dp->numGetRequests;
-    C.nnodes = (uint32_t)c->n;
-    return C;
-}
-
-inline uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
-
-// put (is_put) or get: checks, stages, runs the lookup and the replica phase
-ovs_status dht_batch(ovs_ctx* c, const ovs_dht_params* dp, const ovs_key160* keys, const uint32_t* src, const ovs_dht_op* ops,
-                     uint64_t n, void* out, bool is_put, uint32_t flags, void* stream)
-{
-    static_assert(sizeof(ovs_dht_op) == 32 && sizeof(ovs_dht_put_out) == 24 && sizeof(ovs_dht_get_out) == 40 &&
-                  sizeof(ovs_dht_entry) == 48, "DHT record sizes");
-    if (!c || !dp || (n && (!keys || !src || !ops || !out))) return OVS_EINVAL;
-    ovs_status st = dht_check(c, dp);
-    if (st != OVS_OK) return st;
-    if (n >= 0xFFFFFFFFull) return fail(c, OVS_EINVAL, "DHT batches hold fewer than 2^32 operations");
-    if (n == 0) return OVS_OK;
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    st = check_sources(c, src, n, dev);
-    if (st != OVS_OK) return st;
-    if (!dev) {
-        for (uint64_t i = 0; i < n; ++i) {
-            if (ops[i].t0_ns < 0) return fail(c, OVS_EINVAL, "DHT operation with a negative time");
-            if (ops[i].id == 0)
-                return fail(c, OVS_ENOTSUP, is_put ? "put with id = 0: DHT.cc:869-874 draws a random id; the caller draws it"
-                                                   : "get with id = 0: wildcard gets are not implemented");
-            if (ops[i].kind == 0)
-                return fail(c, OVS_ENOTSUP, is_put ? "put with kind = 0 (DHTDataStorage.cc:170-173 refuses it)"
-                                                   : "get with kind = 0: wildcard gets are not implemented");
-        }
-    }
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    const DhtConsts C = dht_consts(c, dp);
-    const uint64_t np = n * (uint64_t)C.R;
-    CallFrame F(dev, s);
-    const ovs_key160* dk = F.in(keys, n);
-    const uint32_t* ds = F.in(src, n);
-    const ovs_dht_op* dops = F.in(ops, n);
-    ovs_dht_put_out* dput = is_put ? F.out(static_cast<ovs_dht_put_out*>(out), n) : nullptr;
-    ovs_dht_get_out* dget = is_put ? nullptr : F.out(static_cast<ovs_dht_get_out*>(out), n);
-    if (!F.ok()) return frame_fail(c, F);
-    const uint64_t o_sib = up256(sizeof(ovs_lookup_out) * n);
-    const uint64_t o_pt = o_sib + up256(sizeof(uint32_t) * np);
-    const uint64_t o_ps = o_pt + up256(sizeof(long long) * np);
-    CachedBuf::Lease buf = c->dhtb.acquire(is_put ? o_ps + sizeof(uint32_t) * np : o_pt, s);
-    if (!buf) return lease_fail(c, "DHT buffers", buf);
-    ovs_lookup_out* dlook = reinterpret_cast<ovs_lookup_out*>(buf.data());
-    uint32_t* dsib = reinterpret_cast<uint32_t*>(buf.data() + o_sib);
-    // DHT.cc:504-516, 523-535: LookupCall{key, numSiblings = numReplica}, an internal RPC
-    st = ovs_lookup_batch(c, dk, ds, n, C.R, dlook, dsib, OVS_DEVICE_PTRS, s);
-    if (st != OVS_OK) return st;
-    const K160* kk = reinterpret_cast<const K160*>(dk);
-    hipError_t e;
-    DhtHeader h{};
-    if (is_put) {
-        long long* pt = reinterpret_cast<long long*>(buf.data() + o_pt);
-        uint32_t* ps = reinterpret_cast<uint32_t*>(buf.data() + o_ps);
-        e = launch_dht_put_plan(c->dht, C, dlook, dsib, kk, ds, dops, c->xy, n, dput, pt, c->num_cu, s);
-        if (e == hipSuccess) e = launch_dht_put_apply(c->dht, C, dsib, kk, dops, n, pt, ps, c->num_cu, s);
-        if (e == hipSuccess && !dev) e = hipMemcpyAsync(&h, c->dht.hdr, sizeof h, hipMemcpyDeviceToHost, s);
-    } else {
-        e = launch_dht_get(c->dht, C, dlook, dsib, kk, ds, dops, c->xy, n, dget, s);
-    }
-    buf.release();
-    if (e != hipSuccess) return hip_fail(c, e, "DHT kernel");
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    if (h.last_refused)
-        return fail(c, OVS_ENOMEM, "DHT store too small for this put batch (slots in use + pairs without a slot > capacity); "
-                                   "nothing was changed");
-    if (h.last_collisions)
-        return fail(c, OVS_EDEVICE, "DHT store: a put of this batch was dropped, another entry holds its 64-bit tag");
-    return OVS_OK;
-}
-
-}  // namespace
-
-ovs_status ovs_dht_store_create(ovs_ctx* c, uint64_t capacity)
-{
-    if (!c) return OVS_EINVAL;
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (capacity < 1 || capacity >= 0xFFFFFFFFull) return fail(c, OVS_EINVAL, "DHT store capacity outside 1..2^32-2");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->dht.slots) hipFree(c->dht.slots);
-    if (c->dht.hdr) hipFree(c->dht.hdr);
-    c->dht = DhtStore{};
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, sizeof(DhtSlot) * capacity);
-    if (e != hipSuccess) return device_fail(c, e, "DHT store");
-    c->dht.slots = static_cast<DhtSlot*>(p);
-    e = hipMalloc(&p, sizeof(DhtHeader));
-    if (e != hipSuccess) {
-        hipFree(c->dht.slots);
-        c->dht = DhtStore{};
-        return device_fail(c, e, "DHT store header");
-    }
-    c->dht.hdr = static_cast<DhtHeader*>(p);
-    c->dht.cap = capacity;
-    return ovs_dht_store_clear(c);
-}
-
-ovs_status ovs_dht_store_clear(ovs_ctx* c)
-{
-    if (!c) return OVS_EINVAL;
-    if (!c->dht.slots) return fail(c, OVS_ESTATE, "no DHT store: ovs_dht_store_create first");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemsetAsync(c->dht.slots, 0, sizeof(DhtSlot) * c->dht.cap, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->dht.hdr, 0, sizeof(DhtHeader), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return OVS_OK;
-}
-
-ovs_status ovs_dht_store_count(ovs_ctx* c, uint64_t* slots, uint64_t* refused, uint64_t* collisions)
-{
-    if (!c) return OVS_EINVAL;
-    if (!c->dht.slots) return fail(c, OVS_ESTATE, "no DHT store: ovs_dht_store_create first");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());
-    DhtHeader h{};
-    HIPCHK(c, hipMemcpy(&h, c->dht.hdr, sizeof h, hipMemcpyDeviceToHost));
-    if (slots) *slots = h.used;
-    if (refused) *refused = h.refused;
-    if (collisions) *collisions = h.collisions;
-    return OVS_OK;
-}
-
-ovs_status ovs_dht_put_batch(ovs_ctx* c, const ovs_dht_params* dp, const ovs_key160* keys, const uint32_t* src,
-                             const ovs_dht_op* ops, uint64_t n, ovs_dht_put_out* out, uint32_t flags, void* stream)
-{
-    return dht_batch(c, dp, keys, src, ops, n, out, true, flags, stream);
-}
-
-ovs_status ovs_dht_get_batch(ovs_ctx* c, const ovs_dht_params* dp, const ovs_key160* keys, const uint32_t* src,
-                             const ovs_dht_op* ops, uint64_t n, ovs_dht_get_out* out, uint32_t flags, void* stream)
-{
-    return dht_batch(c, dp, keys, src, ops, n, out, false, flags, stream);
-}
-
-// DHTTestApp::handlePutResponse / handleGetResponse / finishApp (DHTTestApp.cc:147-234, 439-467) and the DHT's
-// counters: integer sums on the device (dht.hip), the cStdDevs finished here, the per-node ones in node order
-ovs_status ovs_dhttest_stats_batch(ovs_ctx* c, const ovs_dht_put_out* put_out, const uint32_t* put_src, uint64_t n_put,
-                                   const ovs_dht_get_out* get_out, const ovs_dht_op* get_ops, const uint32_t* get_src,
-                                   const ovs_dhttest_expect* expect, uint64_t n_get, double measured_time_s,
-                                   ovs_dhttest_stats* stats, uint32_t flags, void* stream)
-{
-    static_assert(sizeof(ovs_dhttest_expect) == 24, "ovs_dhttest_expect is 24 B");
-    if (!c || !stats || (n_put && (!put_out || !put_src)) || (n_get && (!get_out || !get_ops || !get_src || !expect)))
-        return OVS_EINVAL;
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (!(measured_time_s >= 0)) return fail(c, OVS_EINVAL, "measured_time_s must be >= 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    CallFrame F(dev, s);
-    const ovs_dht_put_out* dpo = F.in(put_out, n_put);
-    const uint32_t* dps = F.in(put_src, n_put);
-    const ovs_dht_get_out* dgo = F.in(get_out, n_get);
-    const ovs_dht_op* dgp = F.in(get_ops, n_get);
-    const uint32_t* dgs = F.in(get_src, n_get);
-    const ovs_dhttest_expect* dex = F.in(expect, n_get);
-    DhtStatsDev* S = F.scratch<DhtStatsDev>(1);
-    uint32_t* counts = F.scratch<uint32_t>(4 * c->n);
-    if (!F.ok()) return frame_fail(c, F);
-    DhtStatsDev h{};
-    std::vector<uint32_t> nc;
-    try {
-        nc.resize(4 * c->n);
-    } catch (const std::bad_alloc&) {
-        return fail(c, OVS_ENOMEM, "per-node counters");
-    }
-    hipError_t e = launch_dhttest_stats(dpo, dps, n_put, dgo, dgp, dgs, dex, n_get, (uint32_t)c->n, S, counts, c->num_cu, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(nc.data(), counts, sizeof(uint32_t) * nc.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(c, e, "DHTTestApp statistics kernel");
-
-    ovs_dhttest_stats& o = *stats;
-    std::memset(&o, 0, sizeof o);
-    o.num_put_success = h.put_ok; o.num_put_error = h.put_err;
-    o.num_get_success = h.get_ok; o.num_get_error = h.get_err;
-    o.put_latency_sum_ns = h.put_lat; o.put_latency_sumsq_lo = h.put_sq_lo; o.put_latency_sumsq_hi = h.put_sq_hi;
-    o.get_latency_sum_ns = h.get_lat; o.get_latency_sumsq_lo = h.get_sq_lo; o.get_latency_sumsq_hi = h.get_sq_hi;
-    o.get_latency_count = h.get_lat_n;
-    o.put_hop_count = h.put_hop_n; o.put_hop_sum = h.put_hop;
-    o.get_hop_count = h.get_hop_n; o.get_hop_sum = h.get_hop;
-    o.normal_messages = h.msgs; o.num_bytes_normal = h.bytes;
-    // cStdDev of SIMTIME_DBL(latency) from the exact integer sums: sum and sum of squares in seconds
-    auto lat = [](uint64_t cnt, uint64_t sum, uint64_t lo, uint64_t hi, uint64_t mn, uint64_t mx, int64_t* omin, int64_t* omax,
-                  ovs_stddev& d) {
-        if (!cnt) return;
-        *omin = (int64_t)mn; *omax = (int64_t)mx;
-        double r[5];
-        r[0] = (double)sum * 1e-9;
-        r[1] = ((double)hi * 18446744073709551616.0 + (double)lo) * 1e-18;
-        r[2] = (double)mn * 1e-9; r[3] = (double)mx * 1e-9;
-        std::memcpy(&r[4], &cnt, sizeof cnt);
-        finish_stddev(r, 0, d);
-    };
-    lat(h.put_ok, h.put_lat, h.put_sq_lo, h.put_sq_hi, h.put_min, h.put_max, &o.put_latency_min_ns, &o.put_latency_max_ns,
-        o.put_latency_s);
-    lat(h.get_lat_n, h.get_lat, h.get_sq_lo, h.get_sq_hi, h.get_min, h.get_max, &o.get_latency_min_ns, &o.get_latency_max_ns,
-        o.get_latency_s);
-    // DHTTestApp::finishApp (DHTTestApp.cc:439-467) at every node, in node order
-    if (measured_time_s >= 0.1) {
-        double r[5 * 5];
-        uint64_t cnt[5] = {0, 0, 0, 0, 0};
-        for (int k = 0; k < 5; ++k) { r[k * 5 + 0] = 0; r[k * 5 + 1] = 0; r[k * 5 + 2] = INFINITY; r[k * 5 + 3] = -INFINITY; }
-        auto add = [&](int k, double v) {
-            r[k * 5 + 0] += v;
-            r[k * 5 + 1] += v * v;
-            if (v < r[k * 5 + 2]) r[k * 5 + 2] = v;
-            if (v > r[k * 5 + 3]) r[k * 5 + 3] = v;
-            ++cnt[k];
-        };
-        const uint64_t N = c->n;
-        for (uint64_t v = 0; v < N; ++v) {
-            const uint32_t ps = nc[v], pe = nc[N + v], gs = nc[2 * N + v], ge = nc[3 * N + v];
-            add(0, (double)ps / measured_time_s);
-            add(1, (double)pe / measured_time_s);
-            add(2, (double)gs / measured_time_s);
-            add(3, (double)ge / measured_time_s);
-            if (gs + ge > 0) add(4, (double)gs / (double)(gs + ge));
-        }
-        for (int k = 0; k < 5; ++k) std::memcpy(&r[k * 5 + 4], &cnt[k], sizeof(uint64_t));
-        ovs_stddev* sd[5] = {&o.put_success_per_s, &o.put_error_per_s, &o.get_success_per_s, &o.get_error_per_s,
-                             &o.get_success_ratio};
-        for (int k = 0; k < 5; ++k) finish_stddev(r, k, *sd[k]);
-    }
-    return OVS_OK;
-}
-
-// DHTdumpCall (DHT.cc:537-551) is a diagnostic: the table is read back and filtered on the host
-ovs_status ovs_dht_dump_node(ovs_ctx* c, uint32_t node, int64_t now_ns, ovs_dht_entry* entries, uint64_t cap, uint64_t* count)
-{
-    if (!c || !count || (cap && !entries)) return OVS_EINVAL;
-    if (!c->dht.slots) return fail(c, OVS_ESTATE, "no DHT store: ovs_dht_store_create first");
-    if (node >= c->n) return fail(c, OVS_EINVAL, "node outside the network");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());
-    std::vector<DhtSlot> t;
-    try {
-        t.resize(c->dht.cap);
-    } catch (const std::bad_alloc&) {
-        return fail(c, OVS_ENOMEM, "DHT dump");
-    }
-    HIPCHK(c, hipMemcpy(t.data(), c->dht.slots, sizeof(DhtSlot) * c->dht.cap, hipMemcpyDeviceToHost));
-    std::vector<const DhtSlot*> live;
-    for (const DhtSlot& sl : t)
-        if (sl.tag && sl.node == node && sl.vlen > 0 && sl.expiry > now_ns) live.push_back(&sl);
-    std::sort(live.begin(), live.end(), [](const DhtSlot* a, const DhtSlot* b) {
-        if (a->ins_batch != b->ins_batch) return a->ins_batch < b->ins_batch;
-        if (a->ins_t != b->ins_t) return a->ins_t < b->ins_t;
-        return a->ins_op < b->ins_op;
-    });
-    *count = live.size();
-    for (uint64_t i = 0; i < live.size() && i < cap; ++i) {
-        ovs_dht_entry& o = entries[i];
-        std::memcpy(o.key, live[i]->key, sizeof o.key);
-        o.kind = live[i]->kind; o.id = live[i]->id; o.vlen = live[i]->vlen;
-        o.token = live[i]->token; o.expiry_ns = live[i]->expiry;
-    }
-    return OVS_OK;
-}
-
-// Chord overlay broadcasts (BroadcastTestApp.cc:197-340 over Chord::forwardBroadcast, Chord.cc:1410-1445).
-// The level loop: level k's items are queue[lo, hi); its launch appends level k + 1 behind them and
-// the queue length read back is the next hi.  It ends on an empty level or after min(ttl, 161) levels
-// (a node that receives TTL 0 forwards nothing; a path uses each finger level and successor 0 once).
-ovs_status ovs_chord_broadcast_batch(ovs_ctx* c, const uint32_t* initiators, uint64_t nb, int32_t ttl,
-                                     int32_t query_bytes, ovs_bcast_node* nodes, ovs_bcast_stats* stats, uint32_t flags,
-                                     void* stream)
-{
-    if (!c || (nb && !initiators)) return OVS_EINVAL;
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (c->overlay != OVS_OVERLAY_CHORD) return fail(c, OVS_ESTATE, "the broadcast is implemented for Chord rings");
-    if (!c->ideal)
-        return fail(c, OVS_ENOTSUP, "broadcast on explicit tables: the ranges overlap there and the first arrival in time "
-                                    "decides who forwards, which needs a time-ordered replay (converged rings only)");
-    if (c->shard_lo != 0 || c->shard_hi != c->n)
-        return fail(c, OVS_ENOTSUP, "broadcast on one arc of a sharded ring is not implemented");
-    if (ttl < 0 || ttl > 65535) return fail(c, OVS_EINVAL, "ttl must be 0..65535");
-    if (query_bytes < 0) return fail(c, OVS_EINVAL, "query_bytes must be >= 0");
-    ovs_status st = check_common(c, c->P);
-    if (st != OVS_OK) return st;
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    if (!dev)
-        for (uint64_t b = 0; b < nb; ++b)
-            if (initiators[b] >= c->n)
-                return fail(c, OVS_EINVAL, "initiator out of range (broadcast " + std::to_string(b) + ")");
-    if (nb > 0xFFFFFFFFull || nb > (1ull << 38) / c->n) return fail(c, OVS_EINVAL, "too many broadcasts in one batch");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;   // NULL = the default stream
-    if (nb == 0) return OVS_OK;
-    st = ensure_nodes(c, s);
-    if (st != OVS_OK) return st;
-
-    // BROADCASTREQUESTCALL_L = BASECALL_L 256 + query.size() + NODEHANDLE_L 208 + REQUESTID_L 8 + TTL_L 8
-    // bits (CommonMessages.msg:59-71, 90: the query's size in bytes is added as bits); on the wire in a
-    // BaseAppDataMessage (40 bits, no BaseRouteMessage: BaseOverlay.cc:1340-1341) plus UDP/IP 28 B
-    const int64_t call_bits = 480 + (int64_t)query_bytes;
-    const uint64_t call_len = (uint64_t)((call_bits + 7) / 8);
-    const int64_t wire_bytes = (call_bits + 40 + 7) / 8 + 28;
-    // BROADCASTREQUESTRESPONSE_L = BASERESPONSE_L (256 + AUTHBLOCK_L) + REQUESTID_L 8 + 1 bits
-    const uint64_t resp_len = (uint64_t)((265 + (c->P.measureAuthBlock ? 800 : 0) + 7) / 8);
-    BcastConsts BC{};
-    BC.round = c->P.simtimeRound;
-    BC.bw = simtime_host((double)(wire_bytes * 8) / c->P.datarate, c->P.simtimeRound);
-    BC.access2 = 2 * simtime_host(c->P.accessDelay, c->P.simtimeRound);
-
-    const uint64_t cap = nb * c->n;             // every (broadcast, node) is reached at most once
-    CallFrame F(dev, s);
-    const uint32_t* di = F.in(initiators, nb);
-    ovs_bcast_node* dn = nodes ? F.out(nodes, cap) : nullptr;
-    unsigned long long* ctl = F.scratch<unsigned long long>(2);
-    unsigned long long* hist = stats ? F.scratch<unsigned long long>(nb * (BCAST_HIST + 1)) : nullptr;
-    if (!F.ok()) return frame_fail(c, F);
-    const CachedBuf::Lease ql = c->bq.acquire(sizeof(BcastItem) * cap, s);
-    if (!ql) return lease_fail(c, "broadcast queue", ql);
-    BcastItem* queue = reinterpret_cast<BcastItem*>(ql.data());
-
-    HIPCHK(c, hipMemsetAsync(ctl, 0, 2 * sizeof *ctl, s));
-    if (dn) HIPCHK(c, launch_bcast_fill(dn, cap, s));
-    HIPCHK(c, launch_bcast_init(di, nb, (uint32_t)c->n, queue, cap, dn, ctl, s));
-    // a wave per node while the level has fewer nodes than the device has wave slots to fill (their
-    // rows are long there); a lane per node after that.  OVS_BCAST_WAVE_ITEMS moves the switch (A/B, tests)
-    const char* wenv = std::getenv("OVS_BCAST_WAVE_ITEMS");
-    const uint64_t wave_items = wenv ? (uint64_t)std::strtoull(wenv, nullptr, 10) : (uint64_t)c->num_cu * 16;
-    const ChordView V = chord_view(c);
-    const int levels = std::min<int>(ttl, BCAST_MAX_HOPS);
-    unsigned long long h[2] = {0, 0};      // queue length, error bits
-    HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    uint64_t lo = 0, hi = nb;              // level 0: the initiators
-    for (int k = 0; !h[1] && k < levels && hi > lo; ++k) {
-        HIPCHK(c, launch_bcast_level(V, BC, queue, lo, hi, cap, dn, ctl, hi - lo <= wave_items, s));
-        HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        lo = hi;
-        hi = std::min<uint64_t>(h[0], cap);
-    }
-    if (h[1] & BCAST_ERR_INITIATOR) return fail(c, OVS_EINVAL, "initiator out of range");
-    if (h[1]) return fail(c, OVS_EDEVICE, "broadcast queue overflow: a node was reached twice (ring not converged?)");
-    const uint64_t total = hi;
-
-    std::vector<unsigned long long> hh;
-    if (stats) {
-        unsigned long long* last = hist + nb * BCAST_HIST;
-        HIPCHK(c, hipMemsetAsync(hist, 0, sizeof(unsigned long long) * nb * (BCAST_HIST + 1), s));
-        HIPCHK(c, launch_bcast_stats(queue, total, hist, last, s));
-        hh.resize(nb * (BCAST_HIST + 1));
-        HIPCHK(c, hipMemcpyAsync(hh.data(), hist, sizeof(unsigned long long) * hh.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    }
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    for (uint64_t b = 0; stats && b < nb; ++b) {
-        const unsigned long long* hb = &hh[b * BCAST_HIST];
-        ovs_bcast_stats& o = stats[b];
-        std::memset(&o, 0, sizeof o);
-        uint64_t reached = 0, sum = 0, sq = 0;
-        int hmin = -1, hmax = 0;
-        for (int k = 0; k < BCAST_HIST; ++k) {
-            if (!hb[k]) continue;
-            reached += hb[k]; sum += hb[k] * (uint64_t)k; sq += hb[k] * (uint64_t)k * (uint64_t)k;
-            if (hmin < 0) hmin = k;
-            hmax = k;
-        }
-        o.expected = c->n;
-        o.expired = ttl < BCAST_HIST ? hb[ttl] : 0;            // received TTL 0 (BroadcastTestApp.cc:290-299)
-        o.actual = reached - o.expired;
-        o.messages = reached ? 2 * reached - 1 : 0;            // a call per node but the initiator + a response per node
-        // an expired node's response never gets a bit length (BroadcastTestApp.cc:292-297): 0 bytes
-        o.bytes = reached ? (reached - 1) * call_len + o.actual * resp_len : 0;
-        o.last_arrival_ns = (int64_t)hh[nb * BCAST_HIST + b];
-        // cStdDev of "Broadcast: Hop count" (BroadcastTestApp.cc:260), as finish_stddev
-        o.hop_count.count = reached;
-        if (reached) {
-            o.hop_count.mean = (double)sum / (double)reached;
-            double var = 0.0;
-            if (reached > 1) {
-                var = ((double)sq - (double)sum * (double)sum / (double)reached) / (double)(reached - 1);
-                if (var < 0) var = 0;
-            }
-            o.hop_count.stddev = std::sqrt(var);
-            o.hop_count.min = (double)hmin;
-            o.hop_count.max = (double)hmax;
-        }
-    }
-    return OVS_OK;
-}
-
-// ---- Scribe (scribe.hip) ----------------------------------------------------------------------
-namespace {
-extern "C++" {
-
-ovs_status scribe_check(ovs_ctx* c)
-{
-    if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
-    if (c->overlay == OVS_OVERLAY_KADEMLIA) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings, not Kademlia");
-    if (c->overlay == OVS_OVERLAY_KOORDE) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings, not Koorde");
-    if (c->overlay == OVS_OVERLAY_EPICHORD) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings, not EpiChord");
-    if (c->overlay != OVS_OVERLAY_CHORD) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings");
-    if (!c->ideal)
-        return fail(c, OVS_ENOTSUP, "Scribe on explicit tables: the next hop there depends on more than (node, key), so the "
-                                    "tree depends on the order of the joins (converged rings only)");
-    if (c->shard_lo != 0 || c->shard_hi != c->n)
-        return fail(c, OVS_ENOTSUP, "Scribe on one arc of a sharded ring (a shard context) is not implemented");
-    if (c->P.routingType == 2)
-        return fail(c, OVS_ENOTSUP, "Scribe under full-recursive routing: the responses are routed back through forward(), "
-                                    "which is not implemented");
-    if (c->P.routingType == 4)
-        return fail(c, OVS_ENOTSUP, "Scribe under source-routing-recursive routing is not implemented");
-    if (c->P.routingType != 0 && c->P.routingType != 1)
-        return fail(c, OVS_ENOTSUP, "Scribe is implemented for routingType iterative and semi-recursive");
-    ovs_status st = check_common(c, c->P);
-    if (st != OVS_OK) return st;
-    return check_chord_route(c, c->P);
-}
-
-inline uint64_t s_up256(uint64_t b) { return (b + 255) & ~255ull; }
-
-// one allocation for a forest of T tree nodes and G groups
-hipError_t scribe_alloc(ScribeForest& F, uint64_t T, uint64_t G)
-{
-    const uint64_t sz[9] = {8 * T, 4 * T, 4 * T, 4 * T, 4 * (T + 1), 4 * T, 4 * G, 4 * (G + 1), sizeof(K160) * G};
-    uint64_t off[10] = {0};
-    for (int i = 0; i < 9; ++i) off[i + 1] = off[i] + s_up256(sz[i] ? sz[i] : 1);
-    hipError_t e = hipMalloc(&F.block, off[9]);
-    if (e != hipSuccess) { F.block = nullptr; return e; }
-    char* b = static_cast<char*>(F.block);
-    F.key = reinterpret_cast<uint64_t*>(b + off[0]);
-    F.parent = reinterpret_cast<uint32_t*>(b + off[1]);
-    F.ptn = reinterpret_cast<uint32_t*>(b + off[2]);
-    F.info = reinterpret_cast<uint32_t*>(b + off[3]);
-    F.coff = reinterpret_cast<uint32_t*>(b + off[4]);
-    F.cidx = reinterpret_cast<uint32_t*>(b + off[5]);
-    F.root_tn = reinterpret_cast<uint32_t*>(b + off[6]);
-    F.goff = reinterpret_cast<uint32_t*>(b + off[7]);
-    F.gkeys = reinterpret_cast<K160*>(b + off[8]);
-    F.T = T; F.G = G;
-    return hipSuccess;
-}
-
-}  // extern "C++"
-}  // namespace
-
-// The frontier loop: level k's items are q[lo, hi); its launch appends the parents nobody claimed
-// before behind them and the queue length read back is the next hi.  A chain ends at the responsible
-// node, which every hop approaches on a converged ring, so the loop ends on an empty frontier; n
-// levels is the bound.  Everything is built beside the forest in place, which is replaced at the end.
-ovs_status ovs_scribe_build(ovs_ctx* c, const ovs_key160* group_keys, uint64_t G, const uint32_t* member_group,
-                            const uint32_t* member_node, uint64_t nm, uint64_t capacity, uint32_t flags, void* stream)
-{
-    static_assert(sizeof(ovs_scribe_node) == 16 && sizeof(ovs_scribe_msg_out) == 32 && sizeof(ovs_scribe_delivery) == 24,
-                  "Scribe record sizes");
-    if (!c || (G && !group_keys) || (nm && (!member_group || !member_node))) return OVS_EINVAL;
-    ovs_status st = scribe_check(c);
-    if (st != OVS_OK) return st;
-    if (G >= 0x7FFFFFFFull || nm >= 0x7FFFFFFFull || capacity >= 0x7FFFFFFFull)
-        return fail(c, OVS_EINVAL, "too many groups, memberships or tree nodes (31-bit indices)");
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    if (!dev)
-        for (uint64_t i = 0; i < nm; ++i)
-            if (member_group[i] >= G || member_node[i] >= c->n)
-                return fail(c, OVS_EINVAL, "membership " + std::to_string(i) + ": group or node out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    st = ensure_nodes(c, s);
-    if (st != OVS_OK) return st;
-    const uint64_t cap = capacity ? capacity : 1;
-    uint64_t hsize = 64;
-    while (hsize < 2 * cap) hsize <<= 1;
-
-    CallFrame F(dev, s);
-    const K160* dgk = F.in(reinterpret_cast<const K160*>(group_keys), G);
-    const uint32_t* dmg = F.in(member_group, nm);
-    const uint32_t* dmn = F.in(member_node, nm);
-    unsigned long long* tab = F.scratch<unsigned long long>(hsize);
-    uint64_t* q = F.scratch<uint64_t>(cap);
-    uint32_t* par = F.scratch<uint32_t>(cap);
-    unsigned long long* ctl = F.scratch<unsigned long long>(2);
-    if (!F.ok()) return frame_fail(c, F);
-    HIPCHK(c, hipMemsetAsync(tab, 0xFF, sizeof(unsigned long long) * hsize, s));
-    HIPCHK(c, hipMemsetAsync(par, 0xFF, sizeof(uint32_t) * cap, s));
-    HIPCHK(c, hipMemsetAsync(ctl, 0, 2 * sizeof *ctl, s));
-    unsigned long long h[2] = {0, 0};
-    auto read_ctl = [&]() -> hipError_t {
-        hipError_t e = hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s);
-        return e == hipSuccess ? hipStreamSynchronize(s) : e;
-    };
-    auto ctl_status = [&]() -> ovs_status {
-        if (h[1] & SCRIBE_ERR_INPUT) return fail(c, OVS_EINVAL, "a membership's group or node is out of range");
-        if ((h[1] & SCRIBE_ERR_OVERFLOW) || h[0] > capacity)
-            return fail(c, OVS_ENOMEM, "the forest needs more than capacity = " + std::to_string(capacity) + " tree nodes");
-        return OVS_OK;
-    };
-    HIPCHK(c, launch_scribe_init(dmg, dmn, nm, G, (uint32_t)c->n, tab, hsize - 1, q, capacity, ctl, s));
-    HIPCHK(c, read_ctl());
-    if ((st = ctl_status()) != OVS_OK) return st;
-    const uint64_t m0 = h[0];                   // the deduplicated memberships: q[0, m0)
-    const ChordView V = chord_view(c);
-    uint64_t lo = 0, hi = m0;
-    if (c->P.routingType == 0 && m0) {
-        // iterative: nobody forwards (BaseOverlay.cc:1434-1442), every join goes to the responsible node if
-        // its lookup succeeds -- the route kernel's, whose status and responsible node are the parents
-        K160* jk = F.scratch<K160>(m0);
-        uint32_t* js = F.scratch<uint32_t>(m0);
-        ovs_route_out* jr = F.scratch<ovs_route_out>(m0);
-        if (!F.ok()) return frame_fail(c, F);
-        HIPCHK(c, launch_scribe_route_in(dgk, q, m0, jk, js, s));
-        st = ovs_route_batch(c, reinterpret_cast<const ovs_key160*>(jk), js, m0, jr, nullptr, nullptr, OVS_DEVICE_PTRS, s);
-        if (st != OVS_OK) return st;
-        HIPCHK(c, launch_scribe_route_level(jr, q, par, m0, capacity, tab, hsize - 1, ctl, s));
-        HIPCHK(c, read_ctl());
-        if ((st = ctl_status()) != OVS_OK) return st;
-        lo = hi; hi = h[0];
-    }
-    // the hop limit acts on routed join messages only: under iterative routing the levels left are the
-    // responsible nodes' joins through themselves, which a local lookup delivers without a hop check
-    const int join_hcm = c->P.routingType == 0 ? 2 : c->P.hopCountMax;
-    for (uint64_t level = 0; hi > lo && level <= c->n; ++level) {
-        HIPCHK(c, launch_scribe_level(V, dgk, q, par, lo, hi, capacity, tab, hsize - 1, ctl, join_hcm, s));
-        HIPCHK(c, read_ctl());
-        if ((st = ctl_status()) != OVS_OK) return st;
-        lo = hi; hi = h[0];
-    }
-    if (hi > lo) return fail(c, OVS_EDEVICE, "Scribe build: the joins did not end (ring not converged?)");
-    const uint64_t T = hi;
-
-    ScribeForest NF;
-    hipError_t e = scribe_alloc(NF, T, G);
-    if (e != hipSuccess) return device_fail(c, e, "Scribe forest");
-    auto drop = [&](ovs_status r) { hipFree(NF.block); return r; };
-    void* work = nullptr;
-    if ((e = hipMalloc(&work, scribe_finish_bytes(T))) != hipSuccess) return drop(device_fail(c, e, "Scribe sort buffers"));
-    std::vector<uint32_t> goff(G + 1, 0), info(T);
-    if (G) e = hipMemcpyAsync(NF.gkeys, dgk, sizeof(K160) * G, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = launch_scribe_finish(q, par, T, m0, NF, work, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(goff.data(), NF.goff, sizeof(uint32_t) * (G + 1), hipMemcpyDeviceToHost, s);
-    uint32_t E = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&E, NF.coff + T, sizeof E, hipMemcpyDeviceToHost, s);
-    std::vector<uint32_t> roots(G ? G : 1, NONE);
-    if (e == hipSuccess && G) e = hipMemcpyAsync(roots.data(), NF.root_tn, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(work);
-    if (e != hipSuccess) return drop(hip_fail(c, e, "Scribe forest kernels"));
-    if (F.finish() != hipSuccess) return drop(frame_fail(c, F));
-    NF.E = E;
-    NF.routingType = c->P.routingType;
-    NF.hopCountMax = c->P.hopCountMax;
-    for (uint64_t g = 0; g < G; ++g) {
-        NF.roots += roots[g] != NONE;
-        NF.max_tree = std::max<uint64_t>(NF.max_tree, goff[g + 1] - goff[g]);
-    }
-    if (c->scribe.block) hipFree(c->scribe.block);
-    c->scribe = NF;
-    return OVS_OK;
-}
-
-ovs_status ovs_scribe_clear(ovs_ctx* c)
-{
-    if (!c) return OVS_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());
-    if (c->scribe.block) hipFree(c->scribe.block);
-    c->scribe = ScribeForest{};
-    return OVS_OK;
-}
-
-ovs_status ovs_scribe_count(ovs_ctx* c, uint64_t* nodes, uint64_t* edges, uint64_t* rooted)
-{
-    if (!c) return OVS_EINVAL;
-    if (!c->scribe.block) return fail(c, OVS_ESTATE, "no Scribe forest (ovs_scribe_build)");
-    if (nodes) *nodes = c->scribe.T;
-    if (edges) *edges = c->scribe.E;
-    if (rooted) *rooted = c->scribe.roots;
-    return OVS_OK;
-}
-
-ovs_status ovs_scribe_export(ovs_ctx* c, ovs_scribe_node* out, uint32_t flags, void* stream)
-{
-    if (!c) return OVS_EINVAL;
-    if (!c->scribe.block) return fail(c, OVS_ESTATE, "no Scribe forest (ovs_scribe_build)");
-    if (!out && c->scribe.T) return OVS_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    CallFrame F(dev, s);
-    ovs_scribe_node* d = F.out(out, c->scribe.T);
-    if (!F.ok()) return frame_fail(c, F);
-    HIPCHK(c, launch_scribe_export(c->scribe, d, s));
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    return OVS_OK;
-}
-
-// The publish leg is ovs_route_batch itself with the ScribePublishCall (and the data in it) in the
-// KBRTestApp message's place; k_scribe_publish ends it, the level loop walks the child lists as the
-// broadcast's does, k_scribe_collect sums up.
-ovs_status ovs_scribe_multicast_batch(ovs_ctx* c, const uint32_t* msg_group, const uint32_t* msg_src, const uint8_t* msg_flags,
-                                      uint64_t nm, int32_t payload_bytes, ovs_scribe_msg_out* out,
-                                      ovs_scribe_delivery* deliveries, uint64_t deliv_cap, uint64_t* deliv_count,
-                                      uint32_t flags, void* stream)
-{
-    if (!c || (nm && (!msg_group || !msg_src || !msg_flags || !out))) return OVS_EINVAL;
-    ovs_status st = scribe_check(c);
-    if (st != OVS_OK) return st;
-    const ScribeForest& SF = c->scribe;
-    if (!SF.block) return fail(c, OVS_ESTATE, "no Scribe forest (ovs_scribe_build)");
-    if (SF.routingType != c->P.routingType || SF.hopCountMax != c->P.hopCountMax)
-        return fail(c, OVS_ESTATE, "the Scribe forest was built under another routingType or hopCountMax: build it again");
-    if (payload_bytes < 0 || payload_bytes > (1 << 24)) return fail(c, OVS_EINVAL, "payload_bytes must be 0..2^24");
-    if (nm >= 0x7FFFFFFFull) return fail(c, OVS_EINVAL, "too many messages in one batch");
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    if (!dev)
-        for (uint64_t i = 0; i < nm; ++i)
-            if (msg_group[i] >= SF.G || msg_src[i] >= c->n)
-                return fail(c, OVS_EINVAL, "message " + std::to_string(i) + ": group or source out of range");
-    if (deliv_count) *deliv_count = 0;
-    if (nm == 0) return OVS_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    st = ensure_nodes(c, s);
-    if (st != OVS_OK) return st;
-
-    // ScribePublishCall = BASECALL_L 256 bits (ScribeMessage.msg:38) around the ScribeDataMessage, KEY_L 160 +
-    // 8 bits (:43), around the ALM payload: 53 B + payload.  Routed, it rides in a BaseAppDataMessage in a
-    // BaseRouteMessage like the KBRTestApp message (route_bytes); to a known node, in the BaseAppDataMessage
-    // alone (40 bits, BaseOverlay.cc:1340-1341).  ScribePublishResponse = BASECALL_L + 8 bits (:39: the macro
-    // takes BASECALL_L, so measureAuthBlock adds nothing to it); a copy to a child = the ScribeDataMessage.
-    const int32_t call_bytes = 53 + payload_bytes;
-    auto bw = [&](int64_t bytes) { return simtime_host((double)(bytes * 8) / c->P.datarate, c->P.simtimeRound); };
-    ScribeConsts SC{};
-    SC.round = c->P.simtimeRound;
-    SC.nnodes = (uint32_t)c->n;
-    SC.access2 = 2 * simtime_host(c->P.accessDelay, c->P.simtimeRound);
-    SC.bwData = bw(21 + payload_bytes + 5 + 28);
-    SC.bwResp = bw(33 + 5 + 28);
-    SC.msgDirect = 2 * bw(call_bytes + 5 + 28) + SC.access2;
-    if (SC.bwResp >= (1ll << 32)) return fail(c, OVS_EINVAL, "datarate too low (a response takes over 4 s to serialise)");
-
-    const uint64_t cap = std::max<uint64_t>(nm, nm * SF.max_tree);
-    CallFrame F(dev, s);
-    const uint32_t* dg = F.in(msg_group, nm);
-    const uint32_t* ds = F.in(msg_src, nm);
-    const uint8_t* df = F.in(msg_flags, nm);
-    ovs_scribe_msg_out* dout = F.out(out, nm);
-    ovs_scribe_delivery* dd = deliveries && deliv_cap ? F.out(deliveries, deliv_cap) : nullptr;
-    K160* keys = F.scratch<K160>(nm);
-    ovs_route_out* route = F.scratch<ovs_route_out>(nm);
-    unsigned long long* ctl = F.scratch<unsigned long long>(4);
-    if (!F.ok()) return frame_fail(c, F);
-    const CachedBuf::Lease ql = c->scq.acquire(sizeof(ScribeItem) * cap, s);
-    if (!ql) return lease_fail(c, "multicast queue", ql);
-    ScribeItem* queue = reinterpret_cast<ScribeItem*>(ql.data());
-
-    HIPCHK(c, hipMemsetAsync(ctl, 0, 4 * sizeof *ctl, s));
-    HIPCHK(c, launch_scribe_msg_keys(SF, dg, ds, nm, (uint32_t)c->n, keys, ctl, s));
-    unsigned long long h[4] = {0, 0, 0, 0};
-    if (dev) {
-        // device-pointer messages are checked on the device, before the route kernel reads their sources
-        HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (h[1] & SCRIBE_ERR_INPUT) return fail(c, OVS_EINVAL, "a message's group or source is out of range");
-    }
-    // the route reads its message length from the context's parameters: set for this one call and put
-    // back on every path (a context serves one caller at a time, as its error string and cached buffers do)
-    const int32_t saved = c->P.testMsgSize;
-    c->P.testMsgSize = call_bytes;
-    st = ovs_route_batch(c, reinterpret_cast<const ovs_key160*>(keys), ds, nm, route, nullptr, nullptr, OVS_DEVICE_PTRS, s);
-    c->P.testMsgSize = saved;
-    if (st != OVS_OK) return st;
-    HIPCHK(c, launch_scribe_publish(SF, SC, c->xy, route, dg, ds, df, nm, dout, queue, s));
-    h[0] = nm;
-    HIPCHK(c, hipMemcpyAsync(ctl, h, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-    uint64_t lo = 0, hi = nm;
-    for (uint64_t level = 0; !h[1] && hi > lo && level <= SF.T; ++level) {
-        HIPCHK(c, launch_scribe_down(SF, SC, c->xy, queue, lo, hi, cap, ctl, s));
-        HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        lo = hi;
-        hi = std::min<uint64_t>(h[0], cap);
-    }
-    if (h[1]) return fail(c, OVS_EDEVICE, "multicast queue overflow");
-    HIPCHK(c, launch_scribe_collect(SF, queue, hi, dout, dd, dd ? deliv_cap : 0, ctl + 2, s));
-    HIPCHK(c, hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (dd) F.limit(dd, std::min<uint64_t>(h[2], deliv_cap));
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    if (deliv_count) *deliv_count = h[2];
     return OVS_OK;
 }
 

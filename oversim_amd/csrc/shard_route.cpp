@@ -123,7 +123,7 @@ hipEvent_t mk_event(hipEvent_t* e, bool timing)
 #define RCHK(expr)                                                                          \
     do {                                                                                    \
         hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return ctx_fail(c, OVS_EDEVICE, std::string(#expr) + ": " +   \
+        if (e_ != hipSuccess) return fail(c, OVS_EDEVICE, std::string(#expr) + ": " +   \
                                               hipGetErrorString(e_));                        \
     } while (0)
 
@@ -132,7 +132,7 @@ hipEvent_t mk_event(hipEvent_t* e, bool timing)
         const double t_ = now_ms();                                                         \
         const int r_ = (call);                                                              \
         xms += now_ms() - t_;                                                               \
-        if (r_ != 0) return ctx_fail(c, OVS_EDEVICE, std::string("exchange ") + (what) +    \
+        if (r_ != 0) return fail(c, OVS_EDEVICE, std::string("exchange ") + (what) +    \
                                      " failed (" + std::to_string(r_) + ")" +               \
                                      (g_ex_err.empty() ? "" : ": " + g_ex_err));             \
     } while (0)
@@ -140,9 +140,9 @@ hipEvent_t mk_event(hipEvent_t* e, bool timing)
 ovs_status check_exchange(ovs_ctx* c, const ovs_exchange* ex, const uint64_t* shard_lo)
 {
     if (!ex || !ex->allgather_i64 || !ex->alltoallv || !ex->allreduce_sum_i64 || !shard_lo)
-        return ctx_fail(c, OVS_EINVAL, "exchange callbacks and shard_lo are required");
+        return fail(c, OVS_EINVAL, "exchange callbacks and shard_lo are required");
     if (ex->world < 1 || ex->world > 64 || ex->rank >= ex->world)
-        return ctx_fail(c, OVS_EINVAL, "exchange rank / world out of range (world 1..64)");
+        return fail(c, OVS_EINVAL, "exchange rank / world out of range (world 1..64)");
     return OVS_OK;
 }
 
@@ -183,8 +183,8 @@ ovs_status gathered_failure(ovs_ctx* c, const LocalErr& le, const int64_t* M, ui
     for (uint32_t r = 0; r < W; ++r)
         if (M[(size_t)r * stride + slot] != 0) { if (first < 0) first = (int)r; ++nfail; }
     if (nfail == 0) return OVS_OK;
-    if (!le.ok()) return ctx_fail(c, le.st, std::string(what) + ": " + le.msg);
-    return ctx_fail(c, (ovs_status)M[(size_t)first * stride + slot],
+    if (!le.ok()) return fail(c, le.st, std::string(what) + ": " + le.msg);
+    return fail(c, (ovs_status)M[(size_t)first * stride + slot],
                     std::string(what) + ": rank " + std::to_string(first) + " failed (" + std::to_string(nfail) +
                         " rank(s)); its error names the cause");
 }
@@ -198,15 +198,15 @@ ovs_status check_totals(ovs_ctx* c, const ovs_exchange* ex, int64_t have, int64_
     stage("completeness allreduce", 0);
     XCHK(ex->allreduce_sum_i64(ex->user, v, 4), "allreduce");
     if (v[3] != 0) {
-        if (!le.ok()) return ctx_fail(c, le.st, std::string(what) + ": " + le.msg);
-        return ctx_fail(c, OVS_EDEVICE, std::string(what) + ": " + std::to_string(v[3]) +
+        if (!le.ok()) return fail(c, le.st, std::string(what) + ": " + le.msg);
+        return fail(c, OVS_EDEVICE, std::string(what) + ": " + std::to_string(v[3]) +
                                             " other rank(s) failed; their errors name the cause");
     }
     if (v[2] != 0)
-        return ctx_fail(c, OVS_EDEVICE, std::string(what) + ": " + std::to_string(v[2]) +
+        return fail(c, OVS_EDEVICE, std::string(what) + ": " + std::to_string(v[2]) +
                                             " finished records came from exchange rows nobody wrote");
     if (v[0] != v[1])
-        return ctx_fail(c, OVS_EDEVICE, std::string(what) + ": " + std::to_string(v[0]) + " finished records for " +
+        return fail(c, OVS_EDEVICE, std::string(what) + ": " + std::to_string(v[0]) + " finished records for " +
                                             std::to_string(v[1]) + " lookups");
     return OVS_OK;
 }
@@ -331,7 +331,7 @@ ovs_status route_records(ovs_ctx* c, const ovs_exchange* ex, uint64_t n, uint32_
                 int64_t bad[1] = {ensure(B.recv, std::max<size_t>((size_t)tin * RB, RB), cs[k]) != hipSuccess ? 1 : 0};
                 stage("buffer allreduce", rounds);
                 XCHK(ex->allreduce_sum_i64(ex->user, bad, 1), "allreduce");
-                if (bad[0] != 0) return ctx_fail(c, OVS_ENOMEM, std::string(what) + ": receive buffer allocation failed on " +
+                if (bad[0] != 0) return fail(c, OVS_ENOMEM, std::string(what) + ": receive buffer allocation failed on " +
                                                                    std::to_string(bad[0]) + " rank(s)");
             }
             uint64_t off = 0;
@@ -354,7 +354,7 @@ ovs_status route_records(ovs_ctx* c, const ovs_exchange* ex, uint64_t n, uint32_
         if (!any) break;
         if (++rounds > 10000) {
             // every rank counts the same rounds: all stop here
-            return ctx_fail(c, OVS_EDEVICE, std::string(what) + " did not terminate");
+            return fail(c, OVS_EDEVICE, std::string(what) + " did not terminate");
         }
     }
     // the caller's stream continues after every cohort
@@ -434,7 +434,7 @@ ovs_status ovs_kad_shard_route_batch(ovs_ctx* c, const ovs_exchange* ex, const u
     if (num_siblings < -1 && ovs_kad_shard_levels(c) > 0) {
         // one-way routes over replicated top buckets: the lookups migrate (ovs_kad_shard_mig_step)
         const int32_t rb = ovs_kad_shard_rec_bytes(c);
-        if (rb <= 0) return ctx_fail(c, OVS_ESTATE, "no Kademlia network loaded");
+        if (rb <= 0) return fail(c, OVS_ESTATE, "no Kademlia network loaded");
         const uint32_t W = ex->world;
         auto step = [&](int, bool first, const void* in, uint64_t nin, uint64_t b0, void* out, uint64_t cap,
                         unsigned long long* cnt, unsigned long long* dcnt, hipStream_t s) -> ovs_status {
@@ -465,10 +465,10 @@ ovs_status ovs_kad_shard_route_batch(ovs_ctx* c, const ovs_exchange* ex, const u
         XCHK(ex->allreduce_sum_i64(ex->user, v, 2), "allreduce");
         stage("idle", 0);
         if (stats) stats->exchange_ms += xms;
-        if (!le.ok()) return ctx_fail(c, le.st, le.msg);
-        if (v[1] != 0) return ctx_fail(c, OVS_EDEVICE, "sharded Kademlia (migration): another rank failed");
+        if (!le.ok()) return fail(c, le.st, le.msg);
+        if (v[1] != 0) return fail(c, OVS_EDEVICE, "sharded Kademlia (migration): another rank failed");
         if (v[0] != 0)
-            return ctx_fail(c, OVS_EDEVICE, std::to_string(v[0]) + " Kademlia shard errors (table reads off an arc)");
+            return fail(c, OVS_EDEVICE, std::to_string(v[0]) + " Kademlia shard errors (table reads off an arc)");
         return OVS_OK;
     }
     const double t_start = now_ms();
@@ -489,7 +489,7 @@ ovs_status ovs_kad_shard_route_batch(ovs_ctx* c, const ovs_exchange* ex, const u
         if (st != OVS_OK) le.set(st, ovs_last_error(c));
     }
     const int rb = ovs_kad_shard_resp_bytes(c);
-    if (rb <= 0) return ctx_fail(c, OVS_ESTATE, "no Kademlia network loaded");
+    if (rb <= 0) return fail(c, OVS_ESTATE, "no Kademlia network loaded");
     const uint32_t RB = (uint32_t)rb, QB = sizeof(ovs_kad_req);
     // one round sends at most one request per pending-call slot of every lookup
     const uint64_t slots = P.lookupParallelRpcs <= 4 ? (uint64_t)P.lookupParallelRpcs : 8;
@@ -513,7 +513,7 @@ ovs_status ovs_kad_shard_route_batch(ovs_ctx* c, const ovs_exchange* ex, const u
     uint32_t rounds = 0;
     auto rows = [](const DevBuf& b, uint32_t row) { return (int64_t)(b.cap / row); };
     while (true) {
-        if (++rounds > 5000) return ctx_fail(c, OVS_EDEVICE, "sharded Kademlia routing did not terminate");
+        if (++rounds > 5000) return fail(c, OVS_EDEVICE, "sharded Kademlia routing did not terminate");
         std::fill(hc.begin(), hc.end(), 0);
         if (le.ok()) {
             le.hip(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * W, s), "counter reset");
@@ -561,7 +561,7 @@ ovs_status ovs_kad_shard_route_batch(ovs_ctx* c, const ovs_exchange* ex, const u
             stage("buffer allreduce", rounds);
             XCHK(ex->allreduce_sum_i64(ex->user, bad, 1), "allreduce");
             if (bad[0] != 0)
-                return ctx_fail(c, OVS_ENOMEM, "kademlia shard route: exchange buffers failed on " + std::to_string(bad[0]) +
+                return fail(c, OVS_ENOMEM, "kademlia shard route: exchange buffers failed on " + std::to_string(bad[0]) +
                                                    " rank(s)");
         }
         uint64_t oin = 0, oback = 0;
@@ -612,13 +612,13 @@ ovs_status ovs_kad_shard_route_batch(ovs_ctx* c, const ovs_exchange* ex, const u
     stage("completeness allreduce", 0);
     XCHK(ex->allreduce_sum_i64(ex->user, v, 3), "allreduce");
     stage("idle", 0);
-    if (!le.ok()) return ctx_fail(c, le.st, "sharded Kademlia: " + le.msg);
-    if (v[2] != 0) return ctx_fail(c, OVS_EDEVICE, "sharded Kademlia: " + std::to_string(v[2]) + " other rank(s) failed");
+    if (!le.ok()) return fail(c, le.st, "sharded Kademlia: " + le.msg);
+    if (v[2] != 0) return fail(c, OVS_EDEVICE, "sharded Kademlia: " + std::to_string(v[2]) + " other rank(s) failed");
     if (v[1] != 0)
-        return ctx_fail(c, OVS_EDEVICE, std::to_string(v[1]) + " Kademlia shard errors: responses that could not be "
+        return fail(c, OVS_EDEVICE, std::to_string(v[1]) + " Kademlia shard errors: responses that could not be "
                                         "delivered, table reads off an arc, or sources off their rank's arc");
     if (v[0] != 0)
-        return ctx_fail(c, OVS_EDEVICE, "sharded Kademlia: " + std::to_string(hd) + " finished records for " +
+        return fail(c, OVS_EDEVICE, "sharded Kademlia: " + std::to_string(hd) + " finished records for " +
                                             std::to_string(n) + " lookups on this rank (or another rank incomplete)");
     *n_done = hd;
     if (stats) {

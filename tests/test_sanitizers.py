@@ -4,6 +4,7 @@ through every oracle entry point (tests/sanitize_driver.cpp).  SURVEY.md §5: sa
 host code; GPU code is checked by the parity tests.  CPU only."""
 from __future__ import annotations
 
+import math
 import os
 import shutil
 import subprocess
@@ -96,3 +97,71 @@ def test_persist_plan_clean_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
+
+
+def _cstddev(values=None, sums=None):
+    """cStdDev as cstddev.hpp finishes it, in Python floats (IEEE doubles, no contraction) in the same
+    operation order: (count, mean, stddev, min, max); an empty one stays zeroed."""
+    if sums is None:
+        cnt, s, sq, mn, mx = 0, 0.0, 0.0, math.inf, -math.inf
+        for v in values:
+            s += v
+            sq += v * v
+            mn = v if v < mn else mn
+            mx = v if v > mx else mx
+            cnt += 1
+    else:
+        cnt, s, sq, mn, mx = sums
+    if not cnt:
+        return (0, 0.0, 0.0, 0.0, 0.0)
+    var = 0.0
+    if cnt > 1:
+        var = (sq - s * s / float(cnt)) / float(cnt - 1)
+        if var < 0:
+            var = 0.0
+    return (cnt, s / float(cnt), math.sqrt(var), mn, mx)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_cstddev_clean_and_exact_under_asan_ubsan(tmp_path):
+    """The statistics calls' one accumulator (oversim_amd/csrc/cstddev.hpp) built with plain g++ under
+    ASan/UBSan -Werror and -ffp-contract=off (tests/cstddev_driver.cpp): an empty accumulator, one and two
+    values, a variance that rounds below zero and clamps, exact integer sums against collect() over the
+    same samples, and a row in the device layout -- each compared bit for bit with the same operations
+    in Python floats.  No HIP compiler and no HIP library."""
+    exe = tmp_path / "cstddev_driver"
+    c = ["g++", "-std=c++17", "-ffp-contract=off", *SAN, *WARN, "-I", str(ROOT / "oversim_amd" / "csrc"),
+         str(ROOT / "tests" / "cstddev_driver.cpp"), "-o", str(exe)]
+    r = subprocess.run(c, capture_output=True, text=True)
+    assert r.returncode == 0, f"{' '.join(c)}\n{r.stdout}{r.stderr}"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
+    got = {}
+    for line in r.stdout.splitlines():
+        f = line.split()
+        if len(f) == 6:
+            got[f[0]] = (int(f[1]),) + tuple(float.fromhex(x) for x in f[2:])
+    samples = [3, 7, 7, 12, 1, 30]
+    want = {
+        "empty": _cstddev([]),
+        "one": _cstddev([2.5]),
+        "two": _cstddev([1.0, 4.0]),
+        "clamp": _cstddev([0.1, 0.1, 0.1]),
+        "collect": _cstddev([float(v) for v in samples]),
+        "sums": _cstddev(sums=(len(samples), float(sum(samples)), float(sum(v * v for v in samples)),
+                               float(min(samples)), float(max(samples)))),
+        "row": _cstddev(sums=(4, 10.5, 40.25, 0.5, 6.0)),
+        "empty_row": _cstddev([]),
+    }
+    assert set(got) == set(want), sorted(got)
+    for name, w in want.items():
+        g = got[name]
+        assert g[0] == w[0] and all(a.hex() == b.hex() for a, b in zip(g[1:], w[1:])), (name, g, w)
+    # the cases are what they claim to be
+    s = 0.1 + 0.1 + 0.1
+    sq = 0.1 * 0.1 + 0.1 * 0.1 + 0.1 * 0.1
+    assert sq - s * s / 3.0 < 0 and got["clamp"][2] == 0.0, "three times 0.1 must round to a negative variance and clamp"
+    assert got["one"] == (1, 2.5, 0.0, 2.5, 2.5)
+    assert got["two"][:2] == (2, 2.5) and got["two"][2] == math.sqrt(4.5)
+    assert got["sums"] == got["collect"], "from_sums over exact integer sums must equal collect() over the samples"
