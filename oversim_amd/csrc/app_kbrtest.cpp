@@ -245,10 +245,10 @@ ovs_status ovs_kbrtest_rpc_stats_batch(ovs_ctx* c, const ovs_rpc_out* out, const
     const ovs_rpc_out* dout = F.in(out, n);
     const uint32_t* ds = F.in(src, n);
     const K160* dk = dev || lookup_node_ids ? F.in(reinterpret_cast<const K160*>(keys), n) : nullptr;
-    RpcStatsDev* S = F.scratch<RpcStatsDev>(1);
+    StatsDev* S = F.scratch<StatsDev>(1);
     uint32_t* counts = F.scratch<uint32_t>(3 * c->n);
     if (!F.ok()) return frame_fail(c, F);
-    RpcStatsDev h{};
+    StatsDev h{};
     std::vector<uint32_t> nc;
     if ((st = node_counters(c, 3, nc)) != OVS_OK) return st;
     const hipError_t e = launch_rpc_stats(dout, dk, ds, c->recs, n, (uint32_t)c->n, lookup_node_ids, S, counts, c->num_cu, s);
@@ -261,7 +261,7 @@ ovs_status ovs_kbrtest_rpc_stats_batch(ovs_ctx* c, const ovs_rpc_out* out, const
     o.num_sent = n;
     o.num_delivered = h.delivered;
     o.num_dropped = h.dropped;
-    o.num_timeout = h.timeout;
+    o.num_timeout = h.failed;
     o.bytes_sent = n * B;
     o.bytes_delivered = h.delivered * B;
     o.bytes_dropped = h.dropped * B;

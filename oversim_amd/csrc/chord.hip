@@ -455,8 +455,6 @@ struct Hdr {
     uint64_t gS0, gSL;
 };
 
-__device__ __forceinline__ bool k_zero(const K160& a) { return (a.w[0] | a.w[1] | a.w[2] | a.w[3] | a.w[4]) == 0; }
-
 // orders one wave's LDS stores before its loads of other lanes' slots (and the loads before the
 // next iteration's stores) for the compiler; a wave's LDS instructions execute in issue order
 __device__ __forceinline__ void lds_wave_fence()

@@ -17,11 +17,10 @@
 // interval test and the coordinate delay need no second gather; the test is done on the exact
 // 160-bit distances (the key is in the line already, a 64-bit summary would save nothing).
 //
-// Delay of the j-th request v sends at time t (SimpleNodeEntry.cc:164-194): v's transmit queue is
-// idle when the request arrives (a node receives once and sends only then), the j-th packet has
-// left after (j + 1) serialisation times, and the receiver adds one more:
-//   arrival = t + (j + 2) * T(bits / datarate) + 2 * T(accessDelay) + coordDelay(v, child).
+// Delay of the j-th request v sends at time t: v's transmit queue is idle when the request arrives (a
+// node receives once and sends only then), so it is fanout_arrival (tier_dev.hpp) at rank j.
 #include "chord_bcast.hpp"
+#include "tier_dev.hpp"
 
 namespace ovs {
 
@@ -36,31 +35,14 @@ struct Head {
 
 __device__ __forceinline__ Head load_head(const void* p)
 {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
+    const uint4 b = reinterpret_cast<const uint4*>(p)[1];
     const uint2 c = reinterpret_cast<const uint2*>(p)[4];
     Head h;
-    h.k.w[0] = a.x; h.k.w[1] = a.y; h.k.w[2] = a.z; h.k.w[3] = a.w; h.k.w[4] = b.x;
+    h.k = load_key(p);
     h.aux = b.y;
     h.x = dbl(b.z, b.w);
     h.y = dbl(c.x, c.y);
     return h;
-}
-
-__device__ __forceinline__ K160 load_key(const NodeRec* r)
-{
-    const uint4 a = reinterpret_cast<const uint4*>(r)[0];
-    K160 k;
-    k.w[0] = a.x; k.w[1] = a.y; k.w[2] = a.z; k.w[3] = a.w; k.w[4] = r->w[4];
-    return k;
-}
-
-__device__ __forceinline__ bool k_zero(const K160& a) { return (a.w[0] | a.w[1] | a.w[2] | a.w[3] | a.w[4]) == 0; }
-
-__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src)
-{
-    const unsigned int lo = __shfl((unsigned int)v, src), hi = __shfl((unsigned int)(v >> 32), src);
-    return (unsigned long long)lo | ((unsigned long long)hi << 32);
 }
 
 __device__ __forceinline__ BcastItem load_item(const BcastItem* q)
@@ -121,16 +103,7 @@ __device__ __forceinline__ Sender load_sender(const ChordView& V, const BcastIte
 
 __device__ __forceinline__ int64_t arrival(const BcastConsts& BC, int64_t t, int rank, const Head& a, const Head& b)
 {
-    return t + (int64_t)(rank + 2) * BC.bw + BC.access2 + coord_ns(a.x, a.y, b.x, b.y, BC.round);
-}
-
-// one reservation of popc(mask) queue slots per wave and step; every lane gets the base
-__device__ __forceinline__ unsigned long long reserve(unsigned long long* ctl, uint64_t mask, int lane)
-{
-    const int leader = __ffsll((long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(&ctl[0], (unsigned long long)__popcll(mask));
-    return shfl64(base, leader);
+    return fanout_arrival(t, (uint32_t)rank, BC.bw, BC.access2, a.x, a.y, b.x, b.y, BC.round);
 }
 
 // Late levels: many nodes with 0-2 children each.  One lane per item walks its row twice: first
@@ -213,7 +186,7 @@ __global__ __launch_bounds__(256) void k_bcast_waves(ChordView V, BcastConsts BC
 {
     const uint64_t i = lo + (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t lt = (1ull << lane) - 1ull;   // spelled as wave_reserve spells it: the compiler keeps one copy
     if (i >= hi) return;                       // the whole wave
     const BcastItem it = load_item(queue + i);
     if (it.node >= V.n) return;
@@ -237,11 +210,11 @@ __global__ __launch_bounds__(256) void k_bcast_waves(ChordView V, BcastConsts BC
         if (!mask) continue;
         const uint64_t below = mask & lt;
         const uint32_t above = __shfl(ci, below ? 63 - __clzll((long long)below) : 0);
-        const unsigned long long base = reserve(ctl, mask, lane);
-        if (ok) {
+        const unsigned long long slot = wave_append(ok, ctl, cap, BCAST_ERR_OVERFLOW);   // one reservation per wave and step
+        if (slot != NO_SLOT) {
             const int rank = jbase + __popcll(below);
-            emit(queue, base + (unsigned long long)__popcll(below), cap, nodes, V.n, ctl, it.b, ci, below ? above : carry,
-                 it.node, (uint32_t)it.hops + 1u, (uint32_t)rank, arrival(BC, it.t, rank, S.v, c));
+            emit(queue, slot, cap, nodes, V.n, ctl, it.b, ci, below ? above : carry, it.node, (uint32_t)it.hops + 1u,
+                 (uint32_t)rank, arrival(BC, it.t, rank, S.v, c));
         }
         carry = __shfl(ci, 63 - __clzll((long long)mask));
         jbase += __popcll(mask);
@@ -299,11 +272,7 @@ __global__ __launch_bounds__(256) void k_bcast_stats(const BcastItem* __restrict
         const unsigned long long k0 = shfl64(key, l0);
         const bool mine = valid && key == k0;
         const uint64_t m = __ballot(mine);
-        unsigned long long t = mine ? (unsigned long long)it.t : 0ull;
-        for (int off = 32; off; off >>= 1) {
-            const unsigned long long o = shfl64(t, lane ^ off);
-            t = o > t ? o : t;
-        }
+        const unsigned long long t = wave_max_u64(mine ? (unsigned long long)it.t : 0ull);   // the other lanes add 0
         if (lane == l0) {
             atomicAdd(&hist[(k0 >> 16) * BCAST_HIST + (k0 & 0xFFFFu)], (unsigned long long)__popcll(m));
             atomicMax(&last[k0 >> 16], t);
@@ -312,13 +281,11 @@ __global__ __launch_bounds__(256) void k_bcast_stats(const BcastItem* __restrict
     }
 }
 
-inline bool grid_ok(uint64_t blocks) { return blocks >= 1 && blocks <= 0x7FFFFFFFull; }
-
 }  // namespace
 
 hipError_t launch_bcast_fill(ovs_bcast_node* nodes, uint64_t total, hipStream_t s)
 {
-    const uint64_t blocks = (total + 255) / 256;
+    const uint64_t blocks = blocks256(total);
     if (!grid_ok(blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bcast_fill, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint4*>(nodes), total);
     return hipGetLastError();
@@ -327,7 +294,7 @@ hipError_t launch_bcast_fill(ovs_bcast_node* nodes, uint64_t total, hipStream_t 
 hipError_t launch_bcast_init(const uint32_t* initiators, uint64_t nb, uint32_t n, BcastItem* queue, uint64_t cap,
                              ovs_bcast_node* nodes, unsigned long long* ctl, hipStream_t s)
 {
-    const uint64_t blocks = (nb + 255) / 256;
+    const uint64_t blocks = blocks256(nb);
     if (!grid_ok(blocks) || nb > 0xFFFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bcast_init, dim3((unsigned)blocks), dim3(256), 0, s, initiators, nb, n, queue, cap, nodes, ctl);
     return hipGetLastError();
@@ -339,7 +306,7 @@ hipError_t launch_bcast_level(const ChordView& V, const BcastConsts& BC, BcastIt
 {
     if (hi <= lo) return hipSuccess;
     const uint64_t cnt = hi - lo;
-    const uint64_t blocks = wave_per_item ? (cnt + 3) / 4 : (cnt + 255) / 256;
+    const uint64_t blocks = wave_per_item ? (cnt + 3) / 4 : blocks256(cnt);
     if (!grid_ok(blocks)) return hipErrorInvalidValue;
     if (wave_per_item)
         hipLaunchKernelGGL(k_bcast_waves, dim3((unsigned)blocks), dim3(256), 0, s, V, BC, queue, lo, hi, cap, nodes, ctl);
@@ -352,7 +319,7 @@ hipError_t launch_bcast_stats(const BcastItem* queue, uint64_t total, unsigned l
                               unsigned long long* last, hipStream_t s)
 {
     if (total == 0) return hipSuccess;
-    const uint64_t blocks = (total + 255) / 256;
+    const uint64_t blocks = blocks256(total);
     if (!grid_ok(blocks)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bcast_stats, dim3((unsigned)blocks), dim3(256), 0, s, queue, total, hist, last);
     return hipGetLastError();

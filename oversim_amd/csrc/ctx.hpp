@@ -128,8 +128,6 @@ ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev);
 ovs_status ensure_nodes(ovs_ctx* c, hipStream_t s);
 ChordView chord_view(const ovs_ctx* c);
 
-inline uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
-
 // ---- the route seam ----
 // P is the context's parameters, or a copy that differs in what one call sets (the message length, the
 // number of siblings); the tables (ensure_nodes, chord_view) always follow the context's.

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dht.hpp"
+#include "tier_dev.hpp"
 
 namespace ovs {
 
@@ -38,12 +39,6 @@ constexpr int HASH_BITS = 20;          // a SHA-1 BinaryValue's size(), added as
 __device__ __forceinline__ int bits_bytes(int bits) { return (bits + 7) >> 3; }            // cPacket::getByteLength
 __device__ __forceinline__ int wire_bytes(int bits) { return bits_bytes(28 * 8 + 40 + bits); }   // + UDP/IP + BASEAPPDATA_L
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return x;
-}
-
 __device__ __forceinline__ uint64_t entry_tag(uint32_t node, const K160& k, uint32_t kind, uint32_t id)
 {
     uint64_t h = mix64(((uint64_t)node << 32 | k.w[0]) + 0x9e3779b97f4a7c15ull);
@@ -55,8 +50,7 @@ __device__ __forceinline__ uint64_t entry_tag(uint32_t node, const K160& k, uint
 
 __device__ __forceinline__ bool slot_is(const DhtSlot* s, uint32_t node, const K160& k, uint32_t kind, uint32_t id)
 {
-    return s->node == node && s->kind == kind && s->id == id && s->key[0] == k.w[0] && s->key[1] == k.w[1] &&
-           s->key[2] == k.w[2] && s->key[3] == k.w[3] && s->key[4] == k.w[4];
+    return s->node == node && s->kind == kind && s->id == id && words_are_key(s->key, k);
 }
 
 // read-only probe: the entry's slot, or NONE
@@ -81,13 +75,6 @@ __device__ __forceinline__ int64_t dht_send(int64_t& txfin, uint32_t a, uint32_t
     txfin = (txfin > now ? txfin : now) + bw;
     const double2 pa = xy[a], pb = xy[b];
     return txfin + C.access + coord_ns(pa.x, pa.y, pb.x, pb.y, C.round) + bw + C.access;
-}
-
-__device__ __forceinline__ uint64_t wsum(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void k_dht_put_plan(DhtStore st, DhtConsts C, const ovs_lookup_out* __restrict__ look,
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(256) void k_dht_put_plan(DhtStore st, DhtConsts C, 
         }
         out[i] = o;
     }
-    need = wsum(need);
+    need = wave_sum_u64(need);
     if ((threadIdx.x & 63) == 0 && need) atomicAdd(&st.hdr->need, (unsigned long long)need);
 }
 
@@ -537,8 +524,9 @@ __global__ __launch_bounds__(256) void k_dhttest_stats(const ovs_dht_put_out* __
         if (ok) ++gok; else ++gerr;
         if (s < nnodes) atomicAdd(&nc[(ok ? 2ull : 3ull) * nnodes + s], 1u);
     }
-    pok = wsum(pok); perr = wsum(perr); gok = wsum(gok); gerr = wsum(gerr); phn = wsum(phn); ph = wsum(ph);
-    ghn = wsum(ghn); gh = wsum(gh); msgs = wsum(msgs); bytes = wsum(bytes); gln = wsum(gln);
+    pok = wave_sum_u64(pok); perr = wave_sum_u64(perr); gok = wave_sum_u64(gok); gerr = wave_sum_u64(gerr);
+    phn = wave_sum_u64(phn); ph = wave_sum_u64(ph); ghn = wave_sum_u64(ghn); gh = wave_sum_u64(gh);
+    msgs = wave_sum_u64(msgs); bytes = wave_sum_u64(bytes); gln = wave_sum_u64(gln);
     if ((threadIdx.x & 63) == 0) {
         if (pok) atomicAdd(&S->put_ok, (unsigned long long)pok);
         if (perr) atomicAdd(&S->put_err, (unsigned long long)perr);
@@ -554,13 +542,6 @@ __global__ __launch_bounds__(256) void k_dhttest_stats(const ovs_dht_put_out* __
     }
 }
 
-unsigned grid_for(uint64_t n, int per_block, int num_cu, int per_cu)
-{
-    uint64_t blocks = (n + per_block - 1) / per_block;
-    const uint64_t cap = (uint64_t)(num_cu > 0 ? num_cu : 1) * per_cu;
-    return (unsigned)(blocks > cap ? cap : blocks);
-}
-
 }  // namespace
 
 hipError_t launch_dht_put_plan(const DhtStore& st, const DhtConsts& C, const ovs_lookup_out* look, const uint32_t* sib,
@@ -569,7 +550,7 @@ hipError_t launch_dht_put_plan(const DhtStore& st, const DhtConsts& C, const ovs
 {
     if (n == 0) return hipSuccess;
     if (!st.slots || !st.cap || C.R < 1 || C.R > DHT_MAXR || C.nnodes == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_dht_put_plan, dim3(grid_for(n, 256, num_cu, 8)), dim3(256), 0, s, st, C, look, sib, keys, src,
+    hipLaunchKernelGGL(k_dht_put_plan, dim3(capped_grid(n, 256, num_cu, 8)), dim3(256), 0, s, st, C, look, sib, keys, src,
                        ops, xy, n, out, pair_t);
     return hipGetLastError();
 }
@@ -582,8 +563,8 @@ hipError_t launch_dht_put_apply(const DhtStore& st, const DhtConsts& C, const ui
     if (!st.slots || !st.cap) return hipErrorInvalidValue;
     const uint64_t np = n * (uint64_t)C.R;
     if (np) {
-        const uint64_t blocks = (np + 255) / 256;
-        if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+        const uint64_t blocks = blocks256(np);
+        if (!grid_ok(blocks)) return hipErrorInvalidValue;
         const dim3 g((unsigned)blocks), b(256);
         hipLaunchKernelGGL(k_dht_put_claim, g, b, 0, s, st, C, sib, keys, ops, np, pair_t, pair_slot);
         hipLaunchKernelGGL(k_dht_put_op, g, b, 0, s, st, C, np, pair_t, pair_slot);
@@ -613,15 +594,13 @@ hipError_t launch_dhttest_stats(const ovs_dht_put_out* put_out, const uint32_t* 
                                 const ovs_dhttest_expect* expect, uint64_t n_get, uint32_t nnodes, DhtStatsDev* S,
                                 uint32_t* node_counts, int num_cu, hipStream_t s)
 {
-    hipError_t e = hipMemsetAsync(node_counts, 0, sizeof(uint32_t) * 4 * (uint64_t)nnodes, s);
-    if (e != hipSuccess) return e;
     DhtStatsDev init{};
     init.put_min = ~0ull;
     init.get_min = ~0ull;
-    e = hipMemcpyAsync(S, &init, sizeof init, hipMemcpyHostToDevice, s);
+    const hipError_t e = stats_prelude(node_counts, 4, nnodes, S, init, s);
     if (e != hipSuccess) return e;
     if (n_put + n_get == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dhttest_stats, dim3(grid_for(n_put + n_get, 256, num_cu, 8)), dim3(256), 0, s, put_out, put_src,
+    hipLaunchKernelGGL(k_dhttest_stats, dim3(capped_grid(n_put + n_get, 256, num_cu, 8)), dim3(256), 0, s, put_out, put_src,
                        n_put, get_out, get_ops, get_src, expect, n_get, nnodes, S, node_counts);
     return hipGetLastError();
 }

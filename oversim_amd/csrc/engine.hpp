@@ -12,6 +12,9 @@ namespace ovs {
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int KEYBITS = 160;
 
+// the parts of one device allocation start 256 B apart (host code and the launchers that size work buffers)
+inline uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
+
 // ---------------------------------------------------------------------------
 // Per-launch constants derived from ovs_params on the host.  All times are
 // int64 ns (simtime-scale = -9, default.ini:27).

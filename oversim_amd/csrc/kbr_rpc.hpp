@@ -1,4 +1,4 @@
-// kbr_rpc.hpp -- KBRTestApp RPC test: response leg, timeout rule and statistics (internal).
+// kbr_rpc.hpp -- KBRTestApp RPC test: response leg and timeout rule (internal; its statistics: stats.hpp).
 #pragma once
 #include "engine.hpp"
 
@@ -13,14 +13,6 @@ struct RpcConsts {
     uint32_t nnodes;
 };
 
-// device-side integer counters of the RPC statistics
-struct RpcStatsDev {
-    unsigned long long delivered, dropped, timeout, hop_sum, lat_sum;
-    unsigned long long hop_min, hop_max, lat_min, lat_max;
-    unsigned long long status[8];
-    unsigned long long hist[64];
-};
-
 // Pass 1 over the call routes: writes out[i]; full-recursive routing: also the return route's inputs
 // rkeys[i] = ids[src[i]], rsrc[i] = the responder (an unanswered call: src[i], a self-route).
 hipError_t launch_rpc_finish(const ovs_route_out* route, const uint32_t* src, const KeyRec* recs, const double2* xy,
@@ -29,9 +21,5 @@ hipError_t launch_rpc_finish(const ovs_route_out* route, const uint32_t* src, co
 // Pass 2 (full-recursive routing): folds the return routes into out
 hipError_t launch_rpc_fold(const ovs_route_out* ret, const uint32_t* src, const RpcConsts& RC, uint64_t n,
                            ovs_rpc_out* out, int num_cu, hipStream_t s);
-// node_counts: 3 * nnodes u32 (sent, delivered, dropped per node), zeroed here; S: the sums
-hipError_t launch_rpc_stats(const ovs_rpc_out* out, const K160* keys, const uint32_t* src, const KeyRec* recs,
-                            uint64_t n, uint32_t nnodes, int lookup_node_ids, RpcStatsDev* S, uint32_t* node_counts,
-                            int num_cu, hipStream_t s);
 
 }  // namespace ovs

@@ -91,6 +91,8 @@ OVS_HD K160 k_add(const K160& a, const K160& b)
     return r;
 }
 
+OVS_HD bool k_zero(const K160& a) { return (a.w[0] | a.w[1] | a.w[2] | a.w[3] | a.w[4]) == 0; }
+
 OVS_HD K160 k_xor(const K160& a, const K160& b)
 {
     K160 r;

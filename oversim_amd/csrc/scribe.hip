@@ -21,15 +21,15 @@
 // (NodeHandle.cc:118-130: by key first = ascending node index).  ksort.hip bins a batch by its keys'
 // top 14 bits and leaves each bin unordered; a total order needs a full radix sort (hipcub).
 //
-// Dissemination (Scribe.cc:664-704; SimpleNodeEntry.cc:165-183) runs level by level down the lists.
-// A node that receives the data at t with an idle transmit queue sends child k (0-based) its copy at
-// t + (k + 1) serialisations, and the receiver adds one more:
-//   arrival = t + (k + 2) * T(bits / datarate) + 2 * T(accessDelay) + coordDelay(node, child);
-// at the root the ScribePublishResponse is queued ahead (Scribe.cc:392-406), one T(response) more.
+// Dissemination (Scribe.cc:664-704) runs level by level down the lists.  A node that receives the data
+// at t with an idle transmit queue sends child k (0-based) its copy, which arrives at fanout_arrival
+// (tier_dev.hpp) of rank k; at the root the ScribePublishResponse is queued ahead (Scribe.cc:392-406),
+// one T(response) more.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include "scribe.hpp"
+#include "tier_dev.hpp"
 
 namespace ovs {
 
@@ -37,12 +37,6 @@ namespace {
 
 constexpr unsigned long long EMPTY = ~0ull;
 constexpr int MAX_PROBE = 4096;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return x;
-}
 
 // true for the one lane (of any wave) that puts `key` into the set
 __device__ __forceinline__ bool claim(unsigned long long* __restrict__ tab, uint64_t hmask, uint64_t key,
@@ -60,35 +54,12 @@ __device__ __forceinline__ bool claim(unsigned long long* __restrict__ tab, uint
     return false;
 }
 
-__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src)
-{
-    const unsigned int lo = __shfl((unsigned int)v, src), hi = __shfl((unsigned int)(v >> 32), src);
-    return (unsigned long long)lo | ((unsigned long long)hi << 32);
-}
-
 // the claimants of a wave append their keys: one reservation per wave (called by all lanes)
 __device__ __forceinline__ void append(bool won, uint64_t key, uint64_t* __restrict__ q, uint64_t cap,
                                        unsigned long long* ctl)
 {
-    const uint64_t mask = __ballot(won);
-    if (!mask) return;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(&ctl[0], (unsigned long long)__popcll(mask));
-    base = shfl64(base, leader);
-    if (!won) return;
-    const uint64_t slot = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (slot < cap) q[slot] = key;
-    else atomicOr(&ctl[1], SCRIBE_ERR_OVERFLOW);
-}
-
-__device__ __forceinline__ K160 ent_key(const FingerEnt* e)
-{
-    const uint4 a = reinterpret_cast<const uint4*>(e)[0];
-    K160 k;
-    k.w[0] = a.x; k.w[1] = a.y; k.w[2] = a.z; k.w[3] = a.w; k.w[4] = e->w[4];
-    return k;
+    const unsigned long long slot = wave_append(won, ctl, cap, SCRIBE_ERR_OVERFLOW);
+    if (slot != NO_SLOT) q[slot] = key;
 }
 
 // findNode(K, 1, 1)[0] at node c of the converged ring; c itself when it is responsible
@@ -121,7 +92,7 @@ __device__ __forceinline__ uint32_t next_hop(const ChordView& V, uint32_t c, con
             break;
         }
         const FingerEnt* e = V.frow + crec.aux + (uint32_t)(KEYBITS - 1 - i);
-        if (between_LR(ent_key(e), T, K)) return e->idx;
+        if (between_LR(load_key(e), T, K)) return e->idx;
     }
     for (int j = V.ns - 1; j >= 0; --j) {                    // Chord.cc:655-668
         uint32_t sj = c + (uint32_t)j + 1;
@@ -422,7 +393,7 @@ __global__ __launch_bounds__(256) void k_scribe_down(const uint64_t* __restrict_
         for (uint32_t k = lane; k < bcnt; k += 64) {
             const uint32_t ct = cidx[bc0 + k];
             const double2 c = xy[(uint32_t)key[ct]];
-            const int64_t t = (int64_t)bt + (int64_t)(k + 2) * SC.bwData + SC.access2 + coord_ns(px, py, c.x, c.y, SC.round);
+            const int64_t t = fanout_arrival((int64_t)bt, k, SC.bwData, SC.access2, px, py, c.x, c.y, SC.round);
             if (bslot + k < cap) store_item(queue + bslot + k, bm, ct, bh + 1u, t);
             else atomicOr(&ctl[1], SCRIBE_ERR_OVERFLOW);
         }
@@ -431,7 +402,7 @@ __global__ __launch_bounds__(256) void k_scribe_down(const uint64_t* __restrict_
     for (uint32_t k = 0; k < cnt; ++k) {
         const uint32_t ct = cidx[c0 + k];
         const double2 c = xy[(uint32_t)key[ct]];
-        const int64_t t = it.t + (int64_t)(k + 2) * SC.bwData + SC.access2 + coord_ns(pxy.x, pxy.y, c.x, c.y, SC.round);
+        const int64_t t = fanout_arrival(it.t, k, SC.bwData, SC.access2, pxy.x, pxy.y, c.x, c.y, SC.round);
         if (slot + k < cap) store_item(queue + slot + k, it.m, ct, it.hops + 1u, t);
         else atomicOr(&ctl[1], SCRIBE_ERR_OVERFLOW);
     }
@@ -445,7 +416,6 @@ __global__ __launch_bounds__(256) void k_scribe_collect(const uint64_t* __restri
                                                         unsigned long long* dctl)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     bool sub = false;
     ScribeItem it{};
     int64_t t = 0;
@@ -468,23 +438,13 @@ __global__ __launch_bounds__(256) void k_scribe_collect(const uint64_t* __restri
             atomicMax(w, ph | ((it.hops > 0xFFFFu ? 0xFFFFu : it.hops) << 16));
         }
     }
-    const uint64_t mask = __ballot(sub);
-    if (!mask) return;
-    const int leader = __ffsll((long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(&dctl[0], (unsigned long long)__popcll(mask));
-    base = shfl64(base, leader);
-    if (!sub || !deliv) return;
-    const uint64_t slot = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (slot >= dcap) return;
+    const unsigned long long slot = wave_reserve(sub, &dctl[0]);      // dctl[0] counts every delivery, recorded or not
+    if (slot == NO_SLOT || !deliv || slot >= dcap) return;
     uint2* p = reinterpret_cast<uint2*>(deliv + slot);
     p[0] = make_uint2(it.m, (uint32_t)key[it.tn]);
     p[1] = make_uint2(it.hops, 0u);
     p[2] = make_uint2((uint32_t)(uint64_t)t, (uint32_t)((uint64_t)t >> 32));
 }
-
-inline unsigned nblk(uint64_t n) { return (unsigned)((n + 255) / 256); }
-inline bool grid_ok(uint64_t n) { return n >= 1 && (n + 255) / 256 <= 0x7FFFFFFFull; }
 
 }  // namespace
 
@@ -493,8 +453,8 @@ hipError_t launch_scribe_init(const uint32_t* mgroup, const uint32_t* mnode, uin
                               unsigned long long* ctl, hipStream_t s)
 {
     if (nm == 0) return hipSuccess;
-    if (!grid_ok(nm)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_init, dim3(nblk(nm)), dim3(256), 0, s, mgroup, mnode, nm, G, n, tab, hmask, q, cap, ctl);
+    if (!grid_ok(blocks256(nm))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_init, dim3((unsigned)blocks256(nm)), dim3(256), 0, s, mgroup, mnode, nm, G, n, tab, hmask, q, cap, ctl);
     return hipGetLastError();
 }
 
@@ -503,8 +463,8 @@ hipError_t launch_scribe_level(const ChordView& V, const K160* gkeys, uint64_t* 
                                unsigned long long* ctl, int hopCountMax, hipStream_t s)
 {
     if (hi <= lo) return hipSuccess;
-    if (!grid_ok(hi - lo)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_level, dim3(nblk(hi - lo)), dim3(256), 0, s, V, gkeys, q, par, lo, hi, cap, tab, hmask,
+    if (!grid_ok(blocks256(hi - lo))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_level, dim3((unsigned)blocks256(hi - lo)), dim3(256), 0, s, V, gkeys, q, par, lo, hi, cap, tab, hmask,
                        ctl, hopCountMax);
     return hipGetLastError();
 }
@@ -513,8 +473,8 @@ hipError_t launch_scribe_route_in(const K160* gkeys, const uint64_t* q, uint64_t
                                   hipStream_t s)
 {
     if (m0 == 0) return hipSuccess;
-    if (!grid_ok(m0)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_route_in, dim3(nblk(m0)), dim3(256), 0, s, gkeys, q, m0, keys, src);
+    if (!grid_ok(blocks256(m0))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_route_in, dim3((unsigned)blocks256(m0)), dim3(256), 0, s, gkeys, q, m0, keys, src);
     return hipGetLastError();
 }
 
@@ -522,13 +482,12 @@ hipError_t launch_scribe_route_level(const ovs_route_out* route, uint64_t* q, ui
                                      unsigned long long* tab, uint64_t hmask, unsigned long long* ctl, hipStream_t s)
 {
     if (m0 == 0) return hipSuccess;
-    if (!grid_ok(m0)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_route_level, dim3(nblk(m0)), dim3(256), 0, s, route, q, par, m0, cap, tab, hmask, ctl);
+    if (!grid_ok(blocks256(m0))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_route_level, dim3((unsigned)blocks256(m0)), dim3(256), 0, s, route, q, par, m0, cap, tab, hmask, ctl);
     return hipGetLastError();
 }
 
 namespace {
-inline uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
 size_t sort_temp_bytes(uint64_t T)
 {
     size_t a = 0, b = 0;
@@ -571,24 +530,24 @@ hipError_t launch_scribe_finish(const uint64_t* q, const uint32_t* par, uint64_t
     uint64_t* esorted = reinterpret_cast<uint64_t*>(w); w += up256(8 * T);
     size_t tb = sort_temp_bytes(T);
     const uint32_t t32 = (uint32_t)T;
-    hipLaunchKernelGGL(k_iota, dim3(nblk(T)), dim3(256), 0, s, iota, t32);
+    hipLaunchKernelGGL(k_iota, dim3((unsigned)blocks256(T)), dim3(256), 0, s, iota, t32);
     e = hipcub::DeviceRadixSort::SortPairs(w, tb, q, F.key, iota, perm, (int)T, 0, 32 + bits_of(F.G), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_scribe_link, dim3(nblk(T)), dim3(256), 0, s, F.key, perm, par, t32, (uint32_t)m0, F.parent, F.ptn,
+    hipLaunchKernelGGL(k_scribe_link, dim3((unsigned)blocks256(T)), dim3(256), 0, s, F.key, perm, par, t32, (uint32_t)m0, F.parent, F.ptn,
                        F.info, ekey);
     tb = sort_temp_bytes(T);
     e = hipcub::DeviceRadixSort::SortKeys(w, tb, ekey, esorted, (int)T, 0, 32 + bits_of(T), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_scribe_csr, dim3(nblk(T + 1)), dim3(256), 0, s, esorted, F.key, t32, F.ptn, F.coff, F.cidx, F.info,
+    hipLaunchKernelGGL(k_scribe_csr, dim3((unsigned)blocks256(T + 1)), dim3(256), 0, s, esorted, F.key, t32, F.ptn, F.coff, F.cidx, F.info,
                        F.root_tn);
-    hipLaunchKernelGGL(k_scribe_goff, dim3(nblk((uint64_t)G + 1)), dim3(256), 0, s, F.key, t32, G, F.goff);
+    hipLaunchKernelGGL(k_scribe_goff, dim3((unsigned)blocks256((uint64_t)G + 1)), dim3(256), 0, s, F.key, t32, G, F.goff);
     return hipGetLastError();
 }
 
 hipError_t launch_scribe_export(const ScribeForest& F, ovs_scribe_node* out, hipStream_t s)
 {
     if (F.T == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scribe_export, dim3(nblk(F.T)), dim3(256), 0, s, F.key, F.parent, F.info, (uint32_t)F.T, out);
+    hipLaunchKernelGGL(k_scribe_export, dim3((unsigned)blocks256(F.T)), dim3(256), 0, s, F.key, F.parent, F.info, (uint32_t)F.T, out);
     return hipGetLastError();
 }
 
@@ -596,8 +555,8 @@ hipError_t launch_scribe_msg_keys(const ScribeForest& F, const uint32_t* mgroup,
                                   uint32_t n, K160* keys, unsigned long long* ctl, hipStream_t s)
 {
     if (nm == 0) return hipSuccess;
-    if (!grid_ok(nm)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_msg_keys, dim3(nblk(nm)), dim3(256), 0, s, F.gkeys, (uint32_t)F.G, mgroup, msrc, nm, n, keys,
+    if (!grid_ok(blocks256(nm))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_msg_keys, dim3((unsigned)blocks256(nm)), dim3(256), 0, s, F.gkeys, (uint32_t)F.G, mgroup, msrc, nm, n, keys,
                        ctl);
     return hipGetLastError();
 }
@@ -608,8 +567,8 @@ hipError_t launch_scribe_publish(const ScribeForest& F, const ScribeConsts& SC, 
                                  hipStream_t s)
 {
     if (nm == 0) return hipSuccess;
-    if (!grid_ok(nm)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_publish, dim3(nblk(nm)), dim3(256), 0, s, F.key, F.root_tn, (uint32_t)F.G, SC, xy, route,
+    if (!grid_ok(blocks256(nm))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_publish, dim3((unsigned)blocks256(nm)), dim3(256), 0, s, F.key, F.root_tn, (uint32_t)F.G, SC, xy, route,
                        mgroup, msrc, mflags, nm, out, queue);
     return hipGetLastError();
 }
@@ -618,8 +577,8 @@ hipError_t launch_scribe_down(const ScribeForest& F, const ScribeConsts& SC, con
                               uint64_t lo, uint64_t hi, uint64_t cap, unsigned long long* ctl, hipStream_t s)
 {
     if (hi <= lo) return hipSuccess;
-    if (!grid_ok(hi - lo)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_down, dim3(nblk(hi - lo)), dim3(256), 0, s, F.key, F.coff, F.cidx, SC, xy, queue, lo, hi,
+    if (!grid_ok(blocks256(hi - lo))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_down, dim3((unsigned)blocks256(hi - lo)), dim3(256), 0, s, F.key, F.coff, F.cidx, SC, xy, queue, lo, hi,
                        cap, ctl);
     return hipGetLastError();
 }
@@ -629,8 +588,8 @@ hipError_t launch_scribe_collect(const ScribeForest& F, const ScribeItem* queue,
                                  unsigned long long* dctl, hipStream_t s)
 {
     if (total == 0) return hipSuccess;
-    if (!grid_ok(total)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scribe_collect, dim3(nblk(total)), dim3(256), 0, s, F.key, F.info, queue, total, out, deliv, dcap,
+    if (!grid_ok(blocks256(total))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_collect, dim3((unsigned)blocks256(total)), dim3(256), 0, s, F.key, F.info, queue, total, out, deliv, dcap,
                        dctl);
     return hipGetLastError();
 }

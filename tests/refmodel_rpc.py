@@ -200,15 +200,17 @@ INT_FIELDS = ("num_sent", "num_delivered", "num_dropped", "num_timeout", "bytes_
 def rpc_stats(out, ids, keys, src, measured_time_s: float, lookup_node_ids: bool = True, failure_latency: float = 10.0,
               test_msg_size: int = 100) -> dict:
     """KBRTestApp::handleRpcResponse / handleRpcTimeout (KBRTestApp.cc:251-314) over the batch and finishApp
-    (519-545) over the nodes."""
+    (519-545) over the nodes.  A source that is no node (the engine's device-pointer calls do not check
+    them) counts in the sums and in no node's counters, as in the oracle's one-way and lookup statistics."""
     ids, keys = np.asarray(ids), np.asarray(keys)
     nn, n = len(ids), len(out)
-    sent, deliv, drop = ([0] * nn for _ in range(3))
+    sent, deliv, drop = ([0] * (nn + 1) for _ in range(3))
     hops, lats, timeouts = [], [], 0
     status, hist = [0] * 8, [0] * 64
     for i in range(n):
         o, s = out[i], int(src[i])
         status[int(o["status"]) & 7] += 1
+        s = s if s < nn else nn                     # no node: the extra row
         sent[s] += 1
         ok = int(o["outcome"]) == ANSWERED
         timeouts += 0 if ok else 1
@@ -230,6 +232,7 @@ def rpc_stats(out, ids, keys, src, measured_time_s: float, lookup_node_ids: bool
               success_latency_mean_s=sum(lats) / nd * 1e-9 if nd else 0.0,
               total_latency_mean_s=(sum(lats) * 1e-9 + nr * failure_latency) / n if n else 0.0,
               status_count=status, hop_hist=hist)
+    sent, deliv, drop = sent[:nn], deliv[:nn], drop[:nn]
     T = measured_time_s
     if T >= MIN_MEASURED:
         sd = [[d / T for d in deliv], [d * B / T for d in deliv], [r / T for r in drop], [r * B / T for r in drop],

@@ -1,5 +1,5 @@
-"""KBRTestApp RPC-test statistics on the GPU (ovs_kbrtest_rpc_stats_batch; k_kbrtest_rpc_stats,
-oversim_amd/csrc/kbr_rpc.hip) against tests/refmodel_rpc.rpc_stats over reference RPC records: integer
+"""KBRTestApp RPC-test statistics on the GPU (ovs_kbrtest_rpc_stats_batch; k_stats_lookups over the RPC
+records, oversim_amd/csrc/stats.hip) against tests/refmodel_rpc.rpc_stats over reference RPC records: integer
 fields exact, fp64 fields by the rule tests/test_stats.py applies to the one-way statistics (1e-12
 relative / absolute: the reference adds doubles in event order, so its own sums are order dependent)."""
 from __future__ import annotations
@@ -65,7 +65,19 @@ def test_stats_of_the_engines_own_results(engine: KbrEngine):
     load_chord(engine, 1000, 2, 1, 3)
     res = engine.rpcCall(keys[:N_RPC], src[:N_RPC])
     got = engine.kbrtest_rpc_stats(res, keys[:N_RPC], src[:N_RPC], 120.0)
-    check(got, R.rpc_stats(ref[:N_RPC], ring(1000).ids, keys[:N_RPC], src[:N_RPC], 120.0))
+    ids, keys, src = ring(1000).ids, keys[:N_RPC], src[:N_RPC].copy()
+    check(got, R.rpc_stats(ref[:N_RPC], ids, keys, src, 120.0))
+    # crafted on top: two delivered RPCs with the hop counts 63 and 200, which both belong to the last histogram
+    # bucket, and a delivered and a dropped RPC from sources that are no node (in the sums, in no node's counters)
+    out = ref[:N_RPC].copy()
+    ok = (out["outcome"] == R.ANSWERED) & (ids[np.minimum(out["responder"], 999)] == keys).all(axis=1)
+    deliv, drop = np.flatnonzero(ok), np.flatnonzero(~ok)
+    out["hop_count"][deliv[0]], out["hop_count"][deliv[1]] = 63, 200
+    src[deliv[2]], src[drop[0]] = 1000, 0xFFFFFFF0
+    want = R.rpc_stats(out, ids, keys, src, 120.0)
+    assert want["hop_hist"][63] == 2 and want["hop_count_max"] == 200
+    assert want["num_delivered"] == len(deliv) and want["delivery_ratio"]["count"] <= 1000
+    check(engine.kbrtest_rpc_stats(out, keys, src, 120.0), want)
 
 
 def test_bad_times_are_refused_and_results_unchanged(engine: KbrEngine):

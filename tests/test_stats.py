@@ -37,6 +37,28 @@ def _crafted():
     return ids, xy, keys, src, res
 
 
+WIDE = 38          # copies of an 8-record crafted batch: 304 records, more than one 256-thread block, no multiple of 64
+OK8 = (0, 1, 3, 5, 6)   # the delivered / successful records of both crafted batches under lookupNodeIds
+
+
+def _wide(keys, src, res, hop_field):
+    """A crafted batch WIDE times over.  Two delivered records get the hop counts 63 and 200, which both belong to
+    the last histogram bucket; a delivered and a dropped record (copies of #0 and #2, both from node 0) come from
+    sources that are no node: they count in the sums and in no node's counters."""
+    keys, src = np.tile(keys, (WIDE, 1)), np.tile(src, WIDE)
+    res = {f: np.tile(v, (WIDE, 1) if v.ndim == 2 else WIDE) for f, v in res.items()}
+    res[hop_field][8], res[hop_field][16] = 63, 200
+    src[24], src[26] = len(np.load(GOLD / "chord_n9.npz")["ids"]), 0xFFFFFFF0
+    return keys, src, res
+
+
+def _wide_hist(res, hop_field):
+    ok = [i for i in range(8 * WIDE) if i % 8 in OK8]
+    hist = np.bincount(np.minimum(res[hop_field][ok], 63), minlength=64)
+    assert hist[63] == 2
+    return hist
+
+
 def _cstddev(vals):
     n = len(vals)
     if n == 0:
@@ -78,6 +100,14 @@ def test_oracle_stats_hand_counted():
     # measured lifetime below MIN_MEASURED = 0.1 s: no per-node statistics
     st3 = o.kbrtest_stats(res, keys, src, 0.05)
     assert all(st3[f]["count"] == 0 for f in SD_FIELDS)
+    # the wide batch: node 0 misses one delivered and one dropped record, the sums miss nothing
+    wk, ws, wr = _wide(keys, src, res, "one_way_hops")
+    st4 = o.kbrtest_stats(wr, wk, ws, T, lookupNodeIds=True)
+    assert (st4["num_sent"], st4["num_delivered"], st4["num_dropped"], st4["num_lookup_failed"]) == (304, 190, 76, 38)
+    assert st4["hop_count_sum"] == WIDE * sum(int(res["one_way_hops"][i]) for i in delivered) + (63 - 2) + (200 - 2)
+    assert st4["delivered_msgs_per_s"]["mean"] == pytest.approx((190 - 1) / 9 / T, rel=1e-12)
+    assert st4["dropped_msgs_per_s"]["mean"] == pytest.approx((76 - 1) / 9 / T, rel=1e-12)
+    assert st4["delivery_ratio"]["min"] == float(np.float32(1 * WIDE) / np.float32(2 * WIDE))
 
 
 def test_sca_round_trip(tmp_path):
@@ -136,6 +166,14 @@ def test_gpu_stats_crafted(engine):
     assert np.array_equal(np.array(list(g.hop_hist)), hist)
     assert (g.hop_count_min, g.hop_count_max) == (2, 5)
     assert (g.latency_min_ns, g.latency_max_ns) == (7, 3_000_000_000)
+    keys, src, res = _wide(keys, src, res, "one_way_hops")
+    for nid in (True, False):
+        _check(engine.kbrtest_stats(res, keys, src, 2.0, lookupNodeIds=nid),
+               o.kbrtest_stats(res, keys, src, 2.0, lookupNodeIds=nid))
+    g = engine.kbrtest_stats(res, keys, src, 2.0)
+    assert list(g.status_count)[:2] == [7 * WIDE, WIDE]
+    assert np.array_equal(np.array(list(g.hop_hist)), _wide_hist(res, "one_way_hops"))
+    assert (g.hop_count_min, g.hop_count_max) == (2, 200)
 
 
 @pytest.mark.gpu
@@ -216,6 +254,14 @@ def test_oracle_lookup_stats_hand_counted():
     # lookupNodeIds = false: every valid response counts
     st2 = o.kbrtest_lookup_stats(res, keys, src, 2.0, lookupNodeIds=False)
     assert (st2["num_success"], st2["num_failed"], st2["num_invalid"]) == (7, 1, 1)
+    # the wide batch: node 0 misses one successful and one failed lookup, the sums miss nothing
+    wk, ws, wr = _wide(keys, src, res, "hops")
+    st3 = o.kbrtest_lookup_stats(wr, wk, ws, 2.0, lookupNodeIds=True)
+    assert (st3["num_sent"], st3["num_success"], st3["num_failed"], st3["num_invalid"]) == (304, 190, 114, 38)
+    assert st3["hop_count_sum"] == WIDE * sum(int(res["hops"][i]) for i in ok) + (63 - 2) + (200 - 2)
+    assert st3["failed_hop_count_sum"] == WIDE * 8
+    assert st3["successful_lookups_per_s"]["mean"] == pytest.approx((190 - 1) / 9 / 2.0, rel=1e-12)
+    assert st3["failed_lookups_per_s"]["mean"] == pytest.approx((114 - 1) / 9 / 2.0, rel=1e-12)
 
 
 def test_sca_lookup_scalars(tmp_path):
@@ -261,6 +307,14 @@ def test_gpu_lookup_stats_crafted(engine):
     for T, nid in ((2.0, True), (2.0, False), (0.05, True)):
         _check_lookup(engine.kbrtest_lookup_stats(res, keys, src, T, lookupNodeIds=nid),
                       o.kbrtest_lookup_stats(res, keys, src, T, lookupNodeIds=nid))
+    keys, src, res = _wide(keys, src, res, "hops")
+    for nid in (True, False):
+        _check_lookup(engine.kbrtest_lookup_stats(res, keys, src, 2.0, lookupNodeIds=nid),
+                      o.kbrtest_lookup_stats(res, keys, src, 2.0, lookupNodeIds=nid))
+    g = engine.kbrtest_lookup_stats(res, keys, src, 2.0)
+    assert list(g.status_count)[:4] == [7 * WIDE, 0, 0, WIDE]
+    assert np.array_equal(np.array(list(g.hop_hist)), _wide_hist(res, "hops"))
+    assert (g.hop_count_min, g.hop_count_max) == (2, 200)
 
 
 @pytest.mark.gpu
