@@ -763,6 +763,71 @@ ovs_status  ovs_dhttest_stats_batch(ovs_ctx* ctx, const ovs_dht_put_out* put_out
                                     const ovs_dhttest_expect* expect, uint64_t n_get, double measured_time_s,
                                     ovs_dhttest_stats* stats, uint32_t flags, void* stream);
 
+/* ---- Replica-team DHTs (additive to ABI 12; test OVS_HAS_DHT_TEAMS) ----
+ * Replaces, for a batch of independent operations on a converged Chord ring (ovs_chord_load):
+ *   SymmetricDHT::initializeDHT / handlePutCAPIRequest / handleGetCAPIRequest        SymmetricDHT.cc:37-102
+ *   RepeatedHashingDHT::initializeDHT / handlePutCAPIRequest / handleGetCAPIRequest  RepeatedHashingDHT.cc:37-100
+ * One DHTputCAPICall / DHTgetCAPICall becomes numReplicaTeams copies under derived keys (key_0 = key;
+ * symmetric: key_{j+1} = key_j + floor((2^160 - 1) / T) mod 2^160; repeated hashing: key_{j+1} =
+ * SHA-1 of key_j's 40 lowercase hex characters, the digest read big-endian), each with its own
+ * LookupCall for numReplica / T siblings and its own replica RPCs (DHT.cc unchanged, under the team
+ * key), all started at t0 from the same node.  All messages of one operation are replayed in (time,
+ * scheduling order) through one transmit queue per node (SimpleNodeEntry.cc:164-194): the teams'
+ * FindNodeCalls, DHTPutCalls and DHTGetCalls share the source's queue, and a node that answers two
+ * teams has one queue for both answers.  Tier 2 accepts the first team's CAPI response (success or
+ * failure); the other teams run on and their messages and lookups still count.
+ * Accepted: unsharded converged Chord rings, routingType iterative, lookupParallelRpcs = 1,
+ * hopCountMax in 1..1000, 1 <= T <= 8, numReplica % T == 0 (else OVS_EINVAL), 1 <= numReplica <= 8 (all
+ * teams together: an operation has at most 8 replica RPCs), numReplica / T <= getMaxNumSiblings().  Kademlia and explicit Chord tables are OVS_ENOTSUP (the replay needs a
+ * route chain that does not depend on time); so is everything ovs_dht_put_batch refuses. */
+#define OVS_HAS_DHT_TEAMS 1
+enum { OVS_DHT_TEAMS_SYMMETRIC = 0, OVS_DHT_TEAMS_REPEATED_HASHING = 1 };
+typedef struct ovs_dht_team_params {
+    int32_t mode;                /* OVS_DHT_TEAMS_*: **.tier1Type = ...dht.SymmetricDHTModules / ...RepeatedHashingDHTModules */
+    int32_t numReplicaTeams;     /* **.tier1*.dht.numReplicaTeams (1..8); 1 with ...dht.DHTModules */
+} ovs_dht_team_params;
+void        ovs_dht_team_params_default(ovs_dht_team_params* out);   /* symmetric, 1 team */
+/* mode from `**.tier1Type`, numReplicaTeams from `**.tier1*.dht.numReplicaTeams` (forced to 1 for the plain
+ * DHTModules); absent keys leave *tp as it is; any other tier1Type is OVS_ENOTSUP.  config_name, err and the
+ * file form as ovs_params_from_ini / _file. */
+ovs_status  ovs_dht_team_params_from_ini(ovs_dht_team_params* tp, const char* ini_text, const char* config_name,
+                                         char* err, int err_len);
+ovs_status  ovs_dht_team_params_from_ini_file(ovs_dht_team_params* tp, const char* path, const char* config_name,
+                                              char* err, int err_len);
+/* The parameter checks of SymmetricDHT / RepeatedHashingDHT::initializeDHT and of the team calls that need
+ * no network: OVS_EINVAL when numReplica % T != 0, OVS_ENOTSUP for T or numReplica outside 1..8 or an
+ * unknown mode; err may be NULL.  The team calls make the same checks. */
+ovs_status  ovs_dht_team_params_check(const ovs_dht_params* dp, const ovs_dht_team_params* tp, char* err, int err_len);
+/* overlayKeyOffset of SymmetricDHT: floor((2^160 - 1) / T) (OverlayKey.cc:274-279), T in 1..8 */
+ovs_status  ovs_dht_team_offset(int32_t numReplicaTeams, ovs_key160* offset);
+/* team_keys[i * T + j] = key_j of keys[i]: what addresses the store (ovs_dht_dump_node) and GlobalDhtTestMap.
+ * Needs a context (the device) but no network. */
+ovs_status  ovs_dht_team_keys(ovs_ctx* ctx, const ovs_dht_team_params* tp, const ovs_key160* keys, uint64_t n,
+                              ovs_key160* team_keys, uint32_t flags, void* stream);
+/* Arguments as ovs_dht_put_batch / ovs_dht_get_batch (dp->numReplica is the reference's parameter before
+ * initializeDHT divides it) plus tp.  team_out[i * T + j]: team j's record exactly as DHT.cc accounts it,
+ * latency_ns relative to the operation's t0_ns, num_sent counting that team's siblings.  out[i]: the record of
+ * the team whose CAPI response tier 2 accepts, winner[i] its index; out[i].messages / bytes are that team's
+ * share.  The put batch's slot count and its OVS_ENOMEM / `refused` rule are ovs_dht_put_batch's, over the
+ * n * numReplica (operation, team, replica) pairs; entries are stored under the team keys. */
+ovs_status  ovs_dht_team_put_batch(ovs_ctx* ctx, const ovs_dht_params* dp, const ovs_dht_team_params* tp,
+                                   const ovs_key160* keys, const uint32_t* src, const ovs_dht_op* ops, uint64_t n,
+                                   ovs_dht_put_out* out, ovs_dht_put_out* team_out, int32_t* winner, uint32_t flags,
+                                   void* stream);
+ovs_status  ovs_dht_team_get_batch(ovs_ctx* ctx, const ovs_dht_params* dp, const ovs_dht_team_params* tp,
+                                   const ovs_key160* keys, const uint32_t* src, const ovs_dht_op* ops, uint64_t n,
+                                   ovs_dht_get_out* out, ovs_dht_get_out* team_out, int32_t* winner, uint32_t flags,
+                                   void* stream);
+/* ovs_dhttest_stats_batch for team batches: num_put_*, num_get_*, the latency sums and cStdDevs and the
+ * per-node rates from the out records (n_put, n_get of them); the two hop-count vectors (one sample per team
+ * with a valid lookup) and normal_messages / num_bytes_normal from the team_out records (n * T of them). */
+ovs_status  ovs_dhttest_team_stats_batch(ovs_ctx* ctx, const ovs_dht_team_params* tp, const ovs_dht_put_out* put_out,
+                                         const ovs_dht_put_out* put_team_out, const uint32_t* put_src, uint64_t n_put,
+                                         const ovs_dht_get_out* get_out, const ovs_dht_get_out* get_team_out,
+                                         const ovs_dht_op* get_ops, const uint32_t* get_src,
+                                         const ovs_dhttest_expect* expect, uint64_t n_get, double measured_time_s,
+                                         ovs_dhttest_stats* stats, uint32_t flags, void* stream);
+
 /* ---- Chord overlay broadcast (additive to ABI 12; test OVS_HAS_CHORD_BROADCAST) ----
  * Replaces, for a batch of broadcasts on a converged ring (ovs_chord_load):
  *   BroadcastTestApp::initBroadcast / rpcBroadcastRequest  src/tier2/broadcasttestapp/BroadcastTestApp.cc:197-340

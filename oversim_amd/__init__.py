@@ -9,10 +9,11 @@ from .kbr import (BCAST_NODE_DTYPE, DEVICE_PTRS, LOOKUP_OUT_DTYPE, LOOKUP_STATUS
                   OVERLAY_KADEMLIA, ROUTE_OUT_DTYPE, RPC_OUT_DTYPE, BcastStats, KbrEngine, KbrError, KbrTestRpcStats, Network, Params,
                   key_from_int, key_to_int, keys_array, lib)
 from .kbr import DHT_ENTRY_DTYPE, DHT_EXPECT_DTYPE, DHT_GET_DTYPE, DHT_OP_DTYPE, DHT_PUT_DTYPE, DhtParams, DhtTestStats  # noqa: F401
+from .kbr import DHT_TEAMS_REPEATED_HASHING, DHT_TEAMS_SYMMETRIC, DhtTeamParams  # noqa: F401
 from .kbr import SCRIBE_DELIVERY_DTYPE, SCRIBE_MSG_DTYPE, SCRIBE_NODE_DTYPE, SCRIBE_STATUS, ScribeParams  # noqa: F401
 
 __all__ = ["KbrEngine", "KbrError", "Params", "Network", "lib", "keys_array", "key_from_int", "key_to_int",
            "OVERLAY_CHORD", "OVERLAY_KADEMLIA", "ROUTE_OUT_DTYPE", "LOOKUP_OUT_DTYPE", "LOOKUP_STATUS", "NONE", "DEVICE_PTRS",
            "BCAST_NODE_DTYPE", "BcastStats", "RPC_OUT_DTYPE", "KbrTestRpcStats",
            "DhtParams", "DHT_OP_DTYPE", "DHT_PUT_DTYPE", "DHT_GET_DTYPE", "DHT_ENTRY_DTYPE", "DHT_EXPECT_DTYPE",
-           "DhtTestStats", "ScribeParams", "SCRIBE_NODE_DTYPE", "SCRIBE_MSG_DTYPE", "SCRIBE_DELIVERY_DTYPE", "SCRIBE_STATUS"]
+           "DhtTestStats", "DhtTeamParams", "DHT_TEAMS_SYMMETRIC", "DHT_TEAMS_REPEATED_HASHING", "ScribeParams", "SCRIBE_NODE_DTYPE", "SCRIBE_MSG_DTYPE", "SCRIBE_DELIVERY_DTYPE", "SCRIBE_STATUS"]

@@ -5,12 +5,12 @@
 #include <cstring>
 #include <new>
 
+#include "app_dht.hpp"
 #include "cstddev.hpp"
-#include "ctx.hpp"
 
 using namespace ovs;
 
-namespace {
+namespace ovs {
 
 // the tier's own refusals, then the LookupCall's (lookup_check)
 ovs_status dht_check(ovs_ctx* c, const ovs_dht_params* dp, hipStream_t s)
@@ -60,6 +60,69 @@ DhtConsts dht_consts(const ovs_ctx* c, const ovs_dht_params* dp)
     C.nnodes = (uint32_t)c->n;
     return C;
 }
+
+// one launch of the statistics kernel over device records: the sums and, with node_rows, the four per-node
+// counter rows (without: no per-node counting, the sources are not read against the network)
+ovs_status dhttest_sums(ovs_ctx* c, CallFrame& F, const ovs_dht_put_out* dpo, const uint32_t* dps, uint64_t n_put,
+                        const ovs_dht_get_out* dgo, const ovs_dht_op* dgp, const uint32_t* dgs, const ovs_dhttest_expect* dex,
+                        uint64_t n_get, bool node_rows, hipStream_t s, DhtStatsDev* h, std::vector<uint32_t>* nc)
+{
+    const uint64_t N = node_rows ? c->n : 0;
+    DhtStatsDev* S = F.scratch<DhtStatsDev>(1);
+    uint32_t* counts = F.scratch<uint32_t>(4 * N);
+    if (!F.ok()) return frame_fail(c, F);
+    ovs_status st = OVS_OK;
+    nc->assign(1, 0);          // without rows: one word, so that the read-back has somewhere to go
+    if (node_rows && (st = node_counters(c, 4, *nc)) != OVS_OK) return st;
+    const hipError_t e = launch_dhttest_stats(dpo, dps, n_put, dgo, dgp, dgs, dex, n_get, (uint32_t)N, S, counts, c->num_cu, s);
+    return stats_read(c, s, e, h, S, sizeof *h, nc->data(), counts, sizeof(uint32_t) * nc->size(), "DHTTestApp statistics kernel");
+}
+
+void dhttest_finish(const DhtStatsDev& h, const std::vector<uint32_t>& nc, uint64_t N, double measured_time_s,
+                    ovs_dhttest_stats* stats)
+{
+    ovs_dhttest_stats& o = *stats;
+    std::memset(&o, 0, sizeof o);
+    o.num_put_success = h.put_ok; o.num_put_error = h.put_err;
+    o.num_get_success = h.get_ok; o.num_get_error = h.get_err;
+    o.put_latency_sum_ns = h.put_lat; o.put_latency_sumsq_lo = h.put_sq_lo; o.put_latency_sumsq_hi = h.put_sq_hi;
+    o.get_latency_sum_ns = h.get_lat; o.get_latency_sumsq_lo = h.get_sq_lo; o.get_latency_sumsq_hi = h.get_sq_hi;
+    o.get_latency_count = h.get_lat_n;
+    o.put_hop_count = h.put_hop_n; o.put_hop_sum = h.put_hop;
+    o.get_hop_count = h.get_hop_n; o.get_hop_sum = h.get_hop;
+    o.normal_messages = h.msgs; o.num_bytes_normal = h.bytes;
+    // cStdDev of SIMTIME_DBL(latency) from the exact integer sums: sum and sum of squares in seconds
+    auto lat = [](uint64_t cnt, uint64_t sum, uint64_t lo, uint64_t hi, uint64_t mn, uint64_t mx, int64_t* omin, int64_t* omax,
+                  ovs_stddev& d) {
+        if (!cnt) return;
+        *omin = (int64_t)mn; *omax = (int64_t)mx;
+        CStdDev::from_sums(cnt, (double)sum * 1e-9, ((double)hi * 18446744073709551616.0 + (double)lo) * 1e-18,
+                           (double)mn * 1e-9, (double)mx * 1e-9).finish(d);
+    };
+    lat(h.put_ok, h.put_lat, h.put_sq_lo, h.put_sq_hi, h.put_min, h.put_max, &o.put_latency_min_ns, &o.put_latency_max_ns,
+        o.put_latency_s);
+    lat(h.get_lat_n, h.get_lat, h.get_sq_lo, h.get_sq_hi, h.get_min, h.get_max, &o.get_latency_min_ns, &o.get_latency_max_ns,
+        o.get_latency_s);
+    // DHTTestApp::finishApp (DHTTestApp.cc:439-467) at every node, in node order
+    if (measured_time_s >= 0.1) {
+        CStdDev a[5];
+        for (uint64_t v = 0; v < N; ++v) {
+            const uint32_t ps = nc[v], pe = nc[N + v], gs = nc[2 * N + v], ge = nc[3 * N + v];
+            a[0].collect((double)ps / measured_time_s);
+            a[1].collect((double)pe / measured_time_s);
+            a[2].collect((double)gs / measured_time_s);
+            a[3].collect((double)ge / measured_time_s);
+            if (gs + ge > 0) a[4].collect((double)gs / (double)(gs + ge));
+        }
+        ovs_stddev* sd[5] = {&o.put_success_per_s, &o.put_error_per_s, &o.get_success_per_s, &o.get_error_per_s,
+                             &o.get_success_ratio};
+        for (int k = 0; k < 5; ++k) a[k].finish(*sd[k]);
+    }
+}
+
+}  // namespace ovs
+
+namespace {
 
 // put (is_put) or get: checks, stages, runs the lookup and the replica phase
 ovs_status dht_batch(ovs_ctx* c, const ovs_dht_params* dp, const ovs_key160* keys, const uint32_t* src, const ovs_dht_op* ops,
@@ -225,54 +288,11 @@ ovs_status ovs_dhttest_stats_batch(ovs_ctx* c, const ovs_dht_put_out* put_out, c
     const ovs_dht_op* dgp = F.in(get_ops, n_get);
     const uint32_t* dgs = F.in(get_src, n_get);
     const ovs_dhttest_expect* dex = F.in(expect, n_get);
-    DhtStatsDev* S = F.scratch<DhtStatsDev>(1);
-    uint32_t* counts = F.scratch<uint32_t>(4 * c->n);
-    if (!F.ok()) return frame_fail(c, F);
     DhtStatsDev h{};
     std::vector<uint32_t> nc;
-    if ((st = node_counters(c, 4, nc)) != OVS_OK) return st;
-    const hipError_t e = launch_dhttest_stats(dpo, dps, n_put, dgo, dgp, dgs, dex, n_get, (uint32_t)c->n, S, counts, c->num_cu, s);
-    st = stats_read(c, s, e, &h, S, sizeof h, nc.data(), counts, sizeof(uint32_t) * nc.size(), "DHTTestApp statistics kernel");
+    st = dhttest_sums(c, F, dpo, dps, n_put, dgo, dgp, dgs, dex, n_get, true, s, &h, &nc);
     if (st != OVS_OK) return st;
-
-    ovs_dhttest_stats& o = *stats;
-    std::memset(&o, 0, sizeof o);
-    o.num_put_success = h.put_ok; o.num_put_error = h.put_err;
-    o.num_get_success = h.get_ok; o.num_get_error = h.get_err;
-    o.put_latency_sum_ns = h.put_lat; o.put_latency_sumsq_lo = h.put_sq_lo; o.put_latency_sumsq_hi = h.put_sq_hi;
-    o.get_latency_sum_ns = h.get_lat; o.get_latency_sumsq_lo = h.get_sq_lo; o.get_latency_sumsq_hi = h.get_sq_hi;
-    o.get_latency_count = h.get_lat_n;
-    o.put_hop_count = h.put_hop_n; o.put_hop_sum = h.put_hop;
-    o.get_hop_count = h.get_hop_n; o.get_hop_sum = h.get_hop;
-    o.normal_messages = h.msgs; o.num_bytes_normal = h.bytes;
-    // cStdDev of SIMTIME_DBL(latency) from the exact integer sums: sum and sum of squares in seconds
-    auto lat = [](uint64_t cnt, uint64_t sum, uint64_t lo, uint64_t hi, uint64_t mn, uint64_t mx, int64_t* omin, int64_t* omax,
-                  ovs_stddev& d) {
-        if (!cnt) return;
-        *omin = (int64_t)mn; *omax = (int64_t)mx;
-        CStdDev::from_sums(cnt, (double)sum * 1e-9, ((double)hi * 18446744073709551616.0 + (double)lo) * 1e-18,
-                           (double)mn * 1e-9, (double)mx * 1e-9).finish(d);
-    };
-    lat(h.put_ok, h.put_lat, h.put_sq_lo, h.put_sq_hi, h.put_min, h.put_max, &o.put_latency_min_ns, &o.put_latency_max_ns,
-        o.put_latency_s);
-    lat(h.get_lat_n, h.get_lat, h.get_sq_lo, h.get_sq_hi, h.get_min, h.get_max, &o.get_latency_min_ns, &o.get_latency_max_ns,
-        o.get_latency_s);
-    // DHTTestApp::finishApp (DHTTestApp.cc:439-467) at every node, in node order
-    if (measured_time_s >= 0.1) {
-        CStdDev a[5];
-        const uint64_t N = c->n;
-        for (uint64_t v = 0; v < N; ++v) {
-            const uint32_t ps = nc[v], pe = nc[N + v], gs = nc[2 * N + v], ge = nc[3 * N + v];
-            a[0].collect((double)ps / measured_time_s);
-            a[1].collect((double)pe / measured_time_s);
-            a[2].collect((double)gs / measured_time_s);
-            a[3].collect((double)ge / measured_time_s);
-            if (gs + ge > 0) a[4].collect((double)gs / (double)(gs + ge));
-        }
-        ovs_stddev* sd[5] = {&o.put_success_per_s, &o.put_error_per_s, &o.get_success_per_s, &o.get_error_per_s,
-                             &o.get_success_ratio};
-        for (int k = 0; k < 5; ++k) a[k].finish(*sd[k]);
-    }
+    dhttest_finish(h, nc, c->n, measured_time_s, stats);
     return OVS_OK;
 }
 

@@ -33,6 +33,7 @@ struct DhtHeader {
     unsigned long long batch;        // put batches so far
     unsigned long long coll_prev;    // collisions at the start of the last put batch
     unsigned long long last_collisions;   // ... and those of the last put batch alone
+    unsigned long long team_overrun;      // replica-team operations whose replay ran out of its event bound (a defect)
 };
 
 struct DhtStore {

@@ -604,6 +604,54 @@ extern "C" ovs_status ovs_dht_params_from_ini_file(ovs_dht_params* p, int32_t* t
     return ovs_dht_params_from_ini(p, test_ttl, text.c_str(), config_name, err, err_len);
 }
 
+// **.tier1Type and **.tier1*.dht.numReplicaTeams into ovs_dht_team_params; absent keys leave *tp as it is.
+extern "C" ovs_status ovs_dht_team_params_from_ini(ovs_dht_team_params* tp, const char* ini_text, const char* config_name,
+                                                   char* err, int err_len)
+{
+    auto set_err = [&](const std::string& m) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str());
+    };
+    if (!tp || !ini_text) { set_err("null argument"); return OVS_EINVAL; }
+    IniDoc doc;
+    std::string perr, v;
+    const ovs_status ps = doc.parse(ini_text, config_name, &perr);
+    if (ps != OVS_OK) { set_err(perr); return ps; }
+    const std::string host = "SimpleUnderlayNetwork.overlayTerminal[0]";
+    auto ends_with = [](const std::string& a, const std::string& b) {
+        return a.size() >= b.size() && a.compare(a.size() - b.size(), b.size(), b) == 0;
+    };
+    bool plain = false;
+    if (doc.lookup(host + ".tier1Type", &v)) {
+        const std::string t = unquote(v);
+        if (ends_with(t, "dht.SymmetricDHTModules")) tp->mode = OVS_DHT_TEAMS_SYMMETRIC;
+        else if (ends_with(t, "dht.RepeatedHashingDHTModules")) tp->mode = OVS_DHT_TEAMS_REPEATED_HASHING;
+        else if (ends_with(t, "dht.DHTModules")) plain = true;
+        else { set_err("tier1Type is not a DHT: " + t); return OVS_ENOTSUP; }
+    }
+    if (doc.lookup(host + ".tier1.dht.numReplicaTeams", &v) && !to_int(unquote(v), &tp->numReplicaTeams)) {
+        set_err("cannot parse dht parameter numReplicaTeams");
+        return OVS_EINVAL;
+    }
+    if (plain) tp->numReplicaTeams = 1;      // DHT.cc has no teams: one LookupCall under the key itself
+    if (!doc.iter_key.empty()) { set_err("parameter studies (${...}) are not supported: " + doc.iter_key); return OVS_ENOTSUP; }
+    return OVS_OK;
+}
+
+extern "C" ovs_status ovs_dht_team_params_from_ini_file(ovs_dht_team_params* tp, const char* path, const char* config_name,
+                                                        char* err, int err_len)
+{
+    if (!tp || !path) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "null argument");
+        return OVS_EINVAL;
+    }
+    std::string text, e;
+    if (!read_ini_file(path, 0, &text, &e)) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", e.c_str());
+        return OVS_EINVAL;
+    }
+    return ovs_dht_team_params_from_ini(tp, text.c_str(), config_name, err, err_len);
+}
+
 // defaults = the reference's default.ini values (host-only parameter handling, with the binder above)
 extern "C" void ovs_params_default(int32_t overlay, ovs_params* p)
 {

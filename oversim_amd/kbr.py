@@ -239,6 +239,62 @@ class DhtParams(C.Structure):
             setattr(q, k, v)
         return q
 
+DHT_TEAMS_SYMMETRIC, DHT_TEAMS_REPEATED_HASHING = 0, 1
+
+
+class DhtTeamParams(C.Structure):
+    """ovs_dht_team_params: which replica-team DHT (SymmetricDHT.cc / RepeatedHashingDHT.cc) and numReplicaTeams."""
+
+    _fields_ = [("mode", C.c_int32), ("numReplicaTeams", C.c_int32)]
+
+    @classmethod
+    def default(cls) -> "DhtTeamParams":
+        p = cls()
+        lib().ovs_dht_team_params_default(C.byref(p))
+        return p
+
+    @classmethod
+    def symmetric(cls, teams: int) -> "DhtTeamParams":
+        return cls(DHT_TEAMS_SYMMETRIC, teams)
+
+    @classmethod
+    def repeated_hashing(cls, teams: int) -> "DhtTeamParams":
+        return cls(DHT_TEAMS_REPEATED_HASHING, teams)
+
+    @classmethod
+    def from_ini(cls, ini_text: str, config: str | None = None, base: "DhtTeamParams | None" = None) -> "DhtTeamParams":
+        """From .ini text: the mode from `**.tier1Type`, the teams from `**.tier1*.dht.numReplicaTeams`."""
+        return cls._ini(lib().ovs_dht_team_params_from_ini, ini_text.encode(), config, base)
+
+    @classmethod
+    def from_ini_file(cls, path, config: str | None = None, base: "DhtTeamParams | None" = None) -> "DhtTeamParams":
+        return cls._ini(lib().ovs_dht_team_params_from_ini_file, str(path).encode(), config, base)
+
+    @classmethod
+    def _ini(cls, fn, arg, config, base):
+        p = cls.from_buffer_copy(base) if base is not None else cls.default()
+        err = C.create_string_buffer(512)
+        st = fn(C.byref(p), arg, config.encode() if config else None, err, len(err))
+        if st != 0:
+            raise KbrError(f"ovs_dht_team_params_from_ini: {STATUS.get(st, st)}: {err.value.decode()}")
+        return p
+
+    def check(self, dp: "DhtParams") -> None:
+        """The checks of initializeDHT (numReplica a multiple of the teams) and of the team calls' sizes."""
+        err = C.create_string_buffer(512)
+        st = lib().ovs_dht_team_params_check(C.byref(dp), C.byref(self), err, len(err))
+        if st != 0:
+            raise KbrError(f"ovs_dht_team_params_check: {STATUS.get(st, st)}: {err.value.decode()}")
+
+    @staticmethod
+    def offset(teams: int) -> int:
+        """SymmetricDHT's overlayKeyOffset = OverlayKey::getMax() / numReplicaTeams."""
+        w = (C.c_uint32 * 5)()
+        if lib().ovs_dht_team_offset(int(teams), w) != 0:
+            raise KbrError("ovs_dht_team_offset: numReplicaTeams outside 1..8")
+        return sum(int(w[i]) << (32 * i) for i in range(5))
+
+
 class StdDev(C.Structure):
     """ovs_stddev: one cStdDev summary (GlobalStatistics::addStdDev)."""
 
@@ -358,6 +414,15 @@ def lib() -> C.CDLL:
         "ovs_dht_put_batch": ([vp, vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
         "ovs_dht_get_batch": ([vp, vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
         "ovs_dht_dump_node": ([vp, u32, C.c_int64, vp, u64, vp], C.c_int),
+        "ovs_dht_team_params_default": ([vp], None),
+        "ovs_dht_team_params_from_ini": ([vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int], C.c_int),
+        "ovs_dht_team_params_from_ini_file": ([vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int], C.c_int),
+        "ovs_dht_team_params_check": ([vp, vp, C.c_char_p, C.c_int], C.c_int),
+        "ovs_dht_team_offset": ([C.c_int32, vp], C.c_int),
+        "ovs_dht_team_keys": ([vp, vp, vp, u64, vp, u32, vp], C.c_int),
+        "ovs_dht_team_put_batch": ([vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, vp], C.c_int),
+        "ovs_dht_team_get_batch": ([vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, vp], C.c_int),
+        "ovs_dhttest_team_stats_batch": ([vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, C.c_double, vp, u32, vp], C.c_int),
         "ovs_kbrtest_rpc_stats_batch": ([vp, vp, vp, vp, u64, C.c_double, i32, C.c_double, vp, u32, vp], C.c_int),
         "ovs_scribe_build": ([vp, vp, u64, vp, vp, u64, u64, u32, vp], C.c_int),
         "ovs_scribe_clear": ([vp], C.c_int),
@@ -1109,6 +1174,69 @@ class KbrEngine:
             self._chk(self._L.ovs_dht_dump_node(self._h, int(node), int(now_ns), _ptr(out), cnt.value, C.byref(cnt)),
                       "ovs_dht_dump_node")
         return out
+
+    # -- replica-team DHTs (SymmetricDHT.cc / RepeatedHashingDHT.cc)
+    def dht_team_keys(self, keys, tp: DhtTeamParams) -> np.ndarray:
+        """The derived keys, (n, T, 5) uint32: key_0 = key, then + offset (symmetric) or SHA-1 of the hex string."""
+        keys = keys_array(keys)
+        out = np.zeros((len(keys), tp.numReplicaTeams, 5), dtype=np.uint32)
+        self._chk(self._L.ovs_dht_team_keys(self._h, C.byref(tp), _ptr(keys), len(keys), _ptr(out), 0, None),
+                  "ovs_dht_team_keys")
+        return out
+
+    def _dht_team(self, fn, name, dtype, keys, src, ops, tp, dp):
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        ops = np.ascontiguousarray(ops, dtype=DHT_OP_DTYPE)
+        n = len(keys)
+        if not (len(src) == len(ops) == n):
+            raise ValueError("keys, src and ops differ in length")
+        dp = dp if dp is not None else DhtParams.default()
+        T = max(int(tp.numReplicaTeams), 1)
+        out, team, win = np.zeros(n, dtype=dtype), np.zeros((n, T), dtype=dtype), np.zeros(n, dtype=np.int32)
+        self._chk(fn(self._h, C.byref(dp), C.byref(tp), _ptr(keys), _ptr(src), _ptr(ops), n, _ptr(out), _ptr(team), _ptr(win),
+                     0, None), name)
+        return out, team, win
+
+    def dht_team_put(self, keys, src, ops, tp: DhtTeamParams, dp: "DhtParams | None" = None):
+        """Batched puts of a replica-team DHT: (out[n], team_out[n, T], winner[n]); `out` is the record of the team
+        whose DHTputCAPIResponse tier 2 accepts.  dp.numReplica is the value before initializeDHT divides it."""
+        return self._dht_team(self._L.ovs_dht_team_put_batch, "ovs_dht_team_put_batch", DHT_PUT_DTYPE, keys, src, ops, tp, dp)
+
+    def dht_team_get(self, keys, src, ops, tp: DhtTeamParams, dp: "DhtParams | None" = None):
+        """Batched gets of a replica-team DHT: (out[n], team_out[n, T], winner[n])."""
+        return self._dht_team(self._L.ovs_dht_team_get_batch, "ovs_dht_team_get_batch", DHT_GET_DTYPE, keys, src, ops, tp, dp)
+
+    def dht_team_device(self, is_put: bool, keys_ptr: int, src_ptr: int, ops_ptr: int, n: int, out_ptr: int, team_out_ptr: int,
+                        winner_ptr: int, tp: DhtTeamParams, dp: "DhtParams | None" = None, stream: int | None = None):
+        """Device-resident team batch (async on `stream`; a put batch that does not fit is counted by dht_store_count)."""
+        dp = dp if dp is not None else DhtParams.default()
+        fn = self._L.ovs_dht_team_put_batch if is_put else self._L.ovs_dht_team_get_batch
+        self._chk(fn(self._h, C.byref(dp), C.byref(tp), C.c_void_p(keys_ptr), C.c_void_p(src_ptr), C.c_void_p(ops_ptr), n,
+                     C.c_void_p(out_ptr), C.c_void_p(team_out_ptr), C.c_void_p(winner_ptr), DEVICE_PTRS,
+                     C.c_void_p(stream) if stream else None), "ovs_dht_team_put_batch" if is_put else "ovs_dht_team_get_batch")
+
+    def dhttest_team_stats(self, tp: DhtTeamParams, put_out, put_team_out, put_src, get_out, get_team_out, get_ops, get_src,
+                           expect, measured_time_s: float) -> DhtTestStats:
+        """DHTTestApp statistics of a team put batch and a team get batch: outcomes and latencies from the `out`
+        records, hop counts, messages and bytes from the team records."""
+        po = np.ascontiguousarray(put_out, dtype=DHT_PUT_DTYPE)
+        pt = np.ascontiguousarray(put_team_out, dtype=DHT_PUT_DTYPE).reshape(-1)
+        ps = np.ascontiguousarray(put_src, dtype=np.uint32)
+        go = np.ascontiguousarray(get_out, dtype=DHT_GET_DTYPE)
+        gt = np.ascontiguousarray(get_team_out, dtype=DHT_GET_DTYPE).reshape(-1)
+        gp = np.ascontiguousarray(get_ops, dtype=DHT_OP_DTYPE)
+        gs = np.ascontiguousarray(get_src, dtype=np.uint32)
+        ex = np.ascontiguousarray(expect, dtype=DHT_EXPECT_DTYPE)
+        T = int(tp.numReplicaTeams)
+        if len(po) != len(ps) or len(pt) != len(po) * T or not (len(go) == len(gp) == len(gs) == len(ex)) or len(gt) != len(go) * T:
+            raise ValueError("records, sources and expectations differ in length")
+        st = DhtTestStats()
+        self._chk(self._L.ovs_dhttest_team_stats_batch(self._h, C.byref(tp), _ptr(po), _ptr(pt), _ptr(ps), len(po), _ptr(go),
+                                                       _ptr(gt), _ptr(gp), _ptr(gs), _ptr(ex), len(go),
+                                                       float(measured_time_s), C.byref(st), 0, None),
+                  "ovs_dhttest_team_stats_batch")
+        return st
 
     def kbrtest_stats_device(self, out_ptr: int, keys_ptr: int, src_ptr: int, n: int, measured_time_s: float,
                              lookupNodeIds: bool = True, stream: int | None = None) -> KbrTestStats:
