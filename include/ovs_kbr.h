@@ -1214,6 +1214,74 @@ ovs_status  ovs_kad_shard_route_batch(ovs_ctx* ctx, const ovs_exchange* ex, cons
                                       uint32_t* siblings, ovs_shard_route_stats* stats, void* stream);
 #define OVS_KAD_ONEWAY (-2)
 
+/* ---- Broose (src/overlay/broose/; additive to ABI 12; test OVS_HAS_BROOSE) ----
+ * READY Broose nodes with fixed tables: per node 2^brooseShiftingBits + 2 buckets -- rBucket[i]
+ * (key (self >> sb) + (i << (160 - sb)), rBucketSize entries), lBucket (key self << sb, 2^sb *
+ * rBucketSize entries), bBucket (key self, 7 * bucketSize entries) -- each ordered by the XOR of bucket
+ * key and node key (BrooseBucket.cc:49-115, Broose.cc:158-164).  A node's own handle is in its buckets
+ * where it is among their closest (changeState(READY), Broose.cc:233-239).  A batch holds the tables
+ * fixed: findNode's addNode(lastNode) / setLastSeen (675-676) are the caller's to apply between batches
+ * (on the ideal snapshot addNode of a network node changes no bucket).  chooseLookup++ (643) is no
+ * hidden state either: every call takes the direction an extension created in it would get.
+ * Implemented: iterative routing, one-way routes with numSiblings = 1, lookupRedundantNodes =
+ * lookupParallelRpcs = 1, merge off, visitOnlyOnce, hopCountMax >= 1; brooseShiftingBits 1..4,
+ * bucketSize 1..8, 2^sb * rBucketSize <= 64.  Everything else on a Broose context -- ovs_route_batch,
+ * ovs_lookup_batch, ovs_find_node_batch, every application tier -- returns OVS_ENOTSUP; there is no
+ * sharded Broose loader.  ovs_kbrtest_stats_batch takes the route records as they are. */
+#define OVS_HAS_BROOSE 1
+enum { OVS_OVERLAY_BROOSE = 5 };
+typedef struct ovs_broose_params {
+    int32_t bucketSize;         /* **.broose.bucketSize = 8 (default.ini:295) */
+    int32_t rBucketSize;        /* **.broose.rBucketSize = 8 (default.ini:296) */
+    int32_t userDist;           /* **.broose.userDist = 0 (default.ini:297) */
+    int32_t shiftingBits;       /* **.brooseShiftingBits = 2 (default.ini:298) */
+} ovs_broose_params;
+void        ovs_broose_params_default(ovs_broose_params* out);
+/* BrooseFindNodeExtMessage (BrooseMessage.msg): what a Broose FindNodeCall / FindNodeResponse carries.
+ * has_ext = 0: the call carries none yet (the local call of a lookup). */
+typedef struct ovs_broose_ext {
+    uint32_t route_key[5];
+    int32_t  step;
+    uint8_t  has_ext;
+    uint8_t  right_shifting;
+    uint8_t  pad[2];
+    uint32_t last_node;
+} ovs_broose_ext;
+/* rows per node (2^sb + 2: rBucket[0..], lBucket, bBucket) and a row's maxSize; -1 on parameters
+ * outside the implemented ranges */
+int32_t     ovs_broose_num_rows(const ovs_broose_params* bp);
+int32_t     ovs_broose_row_cap(const ovs_broose_params* bp, int32_t row);
+/* The ideal snapshot, built on the device: every bucket of every node holds the maxSize nodes of the
+ * network XOR-closest to its key (fewer on small networks).  params.overlay must be OVS_OVERLAY_BROOSE. */
+ovs_status  ovs_broose_load(ovs_ctx* ctx, const ovs_broose_params* bp, const ovs_key160* ids_sorted, uint64_t n,
+                            const double* xy, uint32_t flags);
+/* Explicit buckets in CSR form (host buffers): row r of node v = row_nodes[row_off[v * rows + r] ..
+ * row_off[v * rows + r + 1]), closest to the bucket key first.  Validated on the host: offsets from 0
+ * and never decreasing, at most the row's maxSize members, members in [0, n), strictly ascending XOR
+ * distance to the bucket key -- else OVS_EINVAL naming the node and row. */
+ovs_status  ovs_broose_load_tables(ovs_ctx* ctx, const ovs_broose_params* bp, const ovs_key160* ids_sorted, uint64_t n,
+                                   const double* xy, const uint64_t* row_off, const uint32_t* row_nodes, uint32_t flags);
+/* The loaded buckets in the same form (host buffers): row_off[n * rows + 1], up to cap members; *total =
+ * how many there are (cap 0 sizes the call; row_nodes may then be NULL). */
+ovs_status  ovs_broose_export(ovs_ctx* ctx, uint64_t* row_off, uint32_t* row_nodes, uint64_t cap, uint64_t* total);
+/* Broose::findNode (Broose.cc:574-770) at node[i] for keys[i] (host buffers).  ext[i]: the call's
+ * extension, replaced by the one the response carries; right[i]: the direction of an extension created
+ * in this call (chooseLookup odd).  numRedundantNodes 1..bucketSize, numSiblings -1..bucketSize (0: the
+ * exact key).  out_nodes[i * max_out ..]: the answer, closest first, 0xFFFFFFFF padded; out_count[i] its
+ * size; out_sibling[i] = isSiblingFor(node, key, numSiblings); out_status[i] = 1 where the reference
+ * errors, reads a bit outside the key or is undefined (left-shifting start with a distance estimate
+ * above 31): no answer then, ext[i] unchanged. */
+ovs_status  ovs_broose_find_node_batch(ovs_ctx* ctx, const uint32_t* node, const ovs_key160* keys, ovs_broose_ext* ext,
+                                       const uint8_t* right, uint64_t n, int32_t numRedundantNodes, int32_t numSiblings,
+                                       uint32_t* out_nodes, uint32_t max_out, uint8_t* out_count, uint8_t* out_sibling,
+                                       uint8_t* out_status);
+/* ovs_route_batch for a Broose context: one-way KBRTestApp routes, right[i] the direction flag of
+ * lookup i.  out / hop_seq / rpcs / flags / stream as for ovs_route_batch; a findNode that the
+ * reference errors on ends its lookup OVS_LOOKUP_BROKEN. */
+ovs_status  ovs_broose_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, const uint8_t* right,
+                                   uint64_t n, ovs_route_out* out, uint32_t* hop_seq, uint32_t* rpcs, uint32_t flags,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ ovs_status ovs_chord_broadcast_batch(ovs_ctx* c, const uint32_t* initiators, uin
 {
     if (!c || (nb && !initiators)) return OVS_EINVAL;
     if (!c->overlay) return fail(c, OVS_ESTATE, "no network loaded");
+    if (c->overlay == OVS_OVERLAY_BROOSE) return fail(c, OVS_ENOTSUP, "the broadcast is implemented for Chord rings, not Broose");
     if (c->overlay != OVS_OVERLAY_CHORD) return fail(c, OVS_ESTATE, "the broadcast is implemented for Chord rings");
     if (!c->ideal)
         return fail(c, OVS_ENOTSUP, "broadcast on explicit tables: the ranges overlap there and the first arrival in time "

@@ -20,6 +20,8 @@ ovs_status dht_check(ovs_ctx* c, const ovs_dht_params* dp, hipStream_t s)
         return fail(c, OVS_ENOTSUP, "DHT on Koorde: LookupCalls (ovs_lookup_batch) are not implemented for Koorde");
     if (c->overlay == OVS_OVERLAY_EPICHORD)
         return fail(c, OVS_ENOTSUP, "DHT on EpiChord: LookupCalls (ovs_lookup_batch) are not implemented for EpiChord");
+    if (c->overlay == OVS_OVERLAY_BROOSE)
+        return fail(c, OVS_ENOTSUP, "DHT on Broose: LookupCalls (ovs_lookup_batch) are not implemented for Broose");
     const bool chord = c->overlay == OVS_OVERLAY_CHORD;
     if (chord ? (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n)) : (c->kad.lo != 0 || c->kad.hi != c->n))
         return fail(c, OVS_ENOTSUP, "DHT on a shard context: the storage and the LookupCall need the whole network on one device");

@@ -10,6 +10,7 @@
 #include <map>
 #include <vector>
 
+#include "broose.hpp"
 #include "call_frame.hpp"
 #include "ctx_internal.hpp"
 #include "dht.hpp"
@@ -61,6 +62,8 @@ struct ovs_ctx {
     ovs::KoordeTables koorde{};
     // epichord routing snapshot (ovs_epichord_load)
     ovs::EpiTables epi{};
+    // broose buckets and records (ovs_broose_load / _load_tables; on the sorted ids in recs / xy)
+    ovs::BrooseTables broose{};
     ovs::CachedBuf kvis;                 // internal visited lists (K3 without hop_seq, K2x without responders)
     // K1's key-order buffers (ksort.hip): sorted keys, sources, caller indices and the sort's
     // histograms, one allocation shared by the calls on this context like kvis
@@ -122,6 +125,13 @@ ovs_status check_chord_route(ovs_ctx* c, const ovs_params& P);
 // host-pointer calls: every lookup's source must be a node of the network (a source past it would
 // be read out of bounds by the lookup kernels); device-pointer calls leave that to the caller (ovs_kbr.h)
 ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev);
+
+// ---- the loaders' common steps (ovs_broose.cpp loads through them too) ----
+// drop the loaded network and everything built on it
+void free_tables(ovs_ctx* c);
+void free_kad_shard(ovs_ctx* c);
+// sorted ids (+ coordinates) into c->recs / c->xy; OVS_EINVAL unless ascending and unique
+ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const double* xy, bool dev);
 
 // ---- the loaded ring ----
 // NodeRec array of an ideal ring for the context's successorListSize (rebuilt when it changes)

@@ -63,7 +63,7 @@ ovs_status hip_fail(ovs_ctx* c, hipError_t e, const char* where)
     return fail(c, OVS_EDEVICE, std::string(where) + ": " + hipGetErrorString(e));
 }
 
-static void free_tables(ovs_ctx* c)
+void free_tables(ovs_ctx* c)
 {
     void* ptrs[] = {c->recs, c->xy, c->fingers, c->pred, c->succ, c->nsucc, c->fres, c->nodes, c->win, c->ftop};
     for (void* p : ptrs)
@@ -74,6 +74,7 @@ static void free_tables(ovs_ctx* c)
     kad_free(c->kad);
     koorde_free(c->koorde);
     epichord_free(c->epi);
+    broose_free(c->broose);
     c->kvis.free();
     c->ks.free();
     c->bq.free();
@@ -91,7 +92,7 @@ static void free_tables(ovs_ctx* c)
     c->kh.clear();
 }
 
-static void free_kad_shard(ovs_ctx* c)
+void free_kad_shard(ovs_ctx* c)
 {
     void* ptrs[] = {c->kst, c->kact, c->kqids, c->kres, c->kbad, c->kiota, c->klist[0], c->klist[1], c->knl,
                     c->kkeys, c->ksrc};
@@ -327,7 +328,7 @@ ovs_status ensure_nodes(ovs_ctx* c, hipStream_t s)
 }
 
 // upload sorted ids (+ coordinates) into KeyRec / double2 arrays
-static ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const double* xy, bool dev)
+ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const double* xy, bool dev)
 {
     if (n < 2) return fail(c, OVS_EINVAL, "need at least 2 nodes");
     if (n >= 0xFFFFFFFFull) return fail(c, OVS_EINVAL, "too many nodes for 32-bit node indices");
@@ -1397,6 +1398,8 @@ ovs_status route_check(ovs_ctx* c, const ovs_params& P, hipStream_t s)
     if (c->overlay == OVS_OVERLAY_EPICHORD)
         return fail(c, OVS_ENOTSUP, "EpiChord lookups rewrite the caches they route over (DESIGN.md §9): "
                                     "ovs_epichord_find_node_batch only");
+    if (c->overlay == OVS_OVERLAY_BROOSE)
+        return fail(c, OVS_ENOTSUP, "Broose: ovs_broose_route_batch and ovs_broose_find_node_batch only");
     ovs_status st = check_common(c, P);
     if (st != OVS_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1518,6 +1521,8 @@ ovs_status lookup_check(ovs_ctx* c, const ovs_params& P0, int32_t num_siblings, 
         return fail(c, OVS_ENOTSUP, "Koorde: ovs_route_batch and ovs_koorde_find_node_batch only");
     if (c->overlay == OVS_OVERLAY_EPICHORD)
         return fail(c, OVS_ENOTSUP, "EpiChord: ovs_epichord_find_node_batch only");
+    if (c->overlay == OVS_OVERLAY_BROOSE)
+        return fail(c, OVS_ENOTSUP, "Broose: ovs_broose_route_batch and ovs_broose_find_node_batch only");
     const bool chord = c->overlay == OVS_OVERLAY_CHORD;
     // BaseOverlay::lookupRpc: numSiblings < 0 -> getMaxNumSiblings() (Chord.cc getMaxNumSiblings =
     // successorListSize, Kademlia.cc:347-350 = s); isSiblingFor rejects larger values
@@ -1991,6 +1996,8 @@ ovs_status ovs_find_node_batch(ovs_ctx* c, const uint32_t* node, const ovs_key16
         return fail(c, OVS_ENOTSUP, "Koorde: ovs_route_batch and ovs_koorde_find_node_batch only");
     if (c->overlay == OVS_OVERLAY_EPICHORD)
         return fail(c, OVS_ENOTSUP, "EpiChord: ovs_epichord_find_node_batch only");
+    if (c->overlay == OVS_OVERLAY_BROOSE)
+        return fail(c, OVS_ENOTSUP, "Broose: ovs_broose_route_batch and ovs_broose_find_node_batch only");
     if (numSiblings > (c->overlay == OVS_OVERLAY_CHORD ? c->P.successorListSize : c->P.s))
         return fail(c, OVS_EINVAL, "numSiblings too big!");
     if (numRedundantNodes < 1 || numRedundantNodes > 64) return fail(c, OVS_EINVAL, "numRedundantNodes out of range");

@@ -35,6 +35,7 @@ OVERLAY_CHORD = 1
 OVERLAY_KADEMLIA = 2
 OVERLAY_KOORDE = 3
 OVERLAY_EPICHORD = 4
+OVERLAY_BROOSE = 5
 DEVICE_PTRS = 0x1
 NONE = 0xFFFFFFFF
 
@@ -93,6 +94,11 @@ class Params(C.Structure):
         return cls.default(OVERLAY_EPICHORD)
 
     @classmethod
+    def broose(cls) -> "Params":
+        """The overlay-independent parameters for a Broose context; Broose's own are BrooseParams."""
+        return cls.default(OVERLAY_BROOSE)
+
+    @classmethod
     def from_ini(cls, text: str, config: str | None = None, overlay: int = OVERLAY_CHORD,
                  base: "Params | None" = None) -> "Params":
         p = cls()
@@ -130,6 +136,9 @@ ROUTE_OUT_DTYPE = np.dtype([("responsible", "<u4"), ("hops", "<u2"), ("status", 
 assert ROUTE_OUT_DTYPE.itemsize == 16
 KOORDE_EXT_DTYPE = np.dtype([("route_key", "<u4", 5), ("step", "<i4"), ("has_route_key", "<i4")])
 assert KOORDE_EXT_DTYPE.itemsize == 28
+BROOSE_EXT_DTYPE = np.dtype([("route_key", "<u4", 5), ("step", "<i4"), ("has_ext", "u1"), ("right_shifting", "u1"),
+                             ("pad", "u1", 2), ("last_node", "<u4")])
+assert BROOSE_EXT_DTYPE.itemsize == 32
 LOOKUP_OUT_DTYPE = np.dtype([("num_siblings", "<u4"), ("hops", "<u2"), ("status", "u1"),
                              ("is_valid", "u1"), ("latency_ns", "<i8")])
 assert LOOKUP_OUT_DTYPE.itemsize == 16
@@ -196,6 +205,30 @@ class ScribeParams:
         if out.messageLength < 0:
             raise ValueError("almTest.messageLength must be >= 0")
         return out
+
+
+class BrooseParams(C.Structure):
+    """ovs_broose_params: **.broose.bucketSize / rBucketSize / userDist and **.brooseShiftingBits."""
+
+    _fields_ = [("bucketSize", C.c_int32), ("rBucketSize", C.c_int32), ("userDist", C.c_int32),
+                ("shiftingBits", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw) -> "BrooseParams":
+        p = cls()
+        lib().ovs_broose_params_default(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+    def num_rows(self) -> int:
+        """rows per node: rBucket[0 .. 2^shiftingBits - 1], lBucket, bBucket"""
+        return int(lib().ovs_broose_num_rows(C.byref(self)))
+
+    def row_cap(self, row: int) -> int:
+        return int(lib().ovs_broose_row_cap(C.byref(self), row))
 
 
 class DhtParams(C.Structure):
@@ -429,6 +462,14 @@ def lib() -> C.CDLL:
         "ovs_scribe_count": ([vp, vp, vp, vp], C.c_int),
         "ovs_scribe_export": ([vp, vp, u32, vp], C.c_int),
         "ovs_scribe_multicast_batch": ([vp, vp, vp, vp, u64, i32, vp, vp, u64, vp, u32, vp], C.c_int),
+        "ovs_broose_params_default": ([vp], None),
+        "ovs_broose_num_rows": ([vp], i32),
+        "ovs_broose_row_cap": ([vp, i32], i32),
+        "ovs_broose_load": ([vp, vp, vp, u64, vp, u32], C.c_int),
+        "ovs_broose_load_tables": ([vp, vp, vp, u64, vp, vp, vp, u32], C.c_int),
+        "ovs_broose_export": ([vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
+        "ovs_broose_find_node_batch": ([vp, vp, vp, vp, vp, u64, i32, i32, vp, u32, vp, vp, vp], C.c_int),
+        "ovs_broose_route_batch": ([vp, vp, vp, vp, u64, vp, vp, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -653,6 +694,120 @@ class KbrEngine:
         self._chk(self._L.ovs_koorde_find_node_batch(self._h, _ptr(node), _ptr(keys), _ptr(ext), _ptr(nxt), n),
                   "ovs_koorde_find_node_batch")
         return nxt, ext
+
+    # -- Broose
+    def broose_load(self, ids, xy, bp: "BrooseParams | None" = None):
+        """The ideal Broose snapshot (ovs_broose_load): every bucket holds the nodes XOR-closest to its key.
+        params.overlay must be OVERLAY_BROOSE."""
+        ids = keys_array(ids)
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        self._bp = bp if bp is not None else BrooseParams.default()
+        self._chk(self._L.ovs_broose_load(self._h, C.byref(self._bp), _ptr(ids), len(ids), _ptr(xy), 0), "ovs_broose_load")
+        self.n, self.overlay = len(ids), OVERLAY_BROOSE
+
+    def broose_load_device(self, ids_ptr: int, xy_ptr: int, n: int, bp: "BrooseParams | None" = None):
+        self._bp = bp if bp is not None else BrooseParams.default()
+        self._chk(self._L.ovs_broose_load(self._h, C.byref(self._bp), C.c_void_p(ids_ptr), n, C.c_void_p(xy_ptr),
+                                          DEVICE_PTRS), "ovs_broose_load")
+        self.n, self.overlay = n, OVERLAY_BROOSE
+
+    def broose_load_tables(self, ids, xy, row_off, row_nodes, bp: "BrooseParams | None" = None):
+        """Explicit Broose buckets in CSR form (ovs_broose_load_tables): row r of node v =
+        row_nodes[row_off[v * rows + r] : row_off[v * rows + r + 1]], closest to the bucket key first."""
+        ids = keys_array(ids)
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        nd = np.ascontiguousarray(row_nodes, dtype=np.uint32)
+        self._bp = bp if bp is not None else BrooseParams.default()
+        if len(off) != len(ids) * self._bp.num_rows() + 1:
+            raise ValueError("row_off must have n * rows + 1 entries")
+        if len(nd) < int(off[-1]):
+            raise ValueError("row_nodes is shorter than row_off[-1]")
+        self._chk(self._L.ovs_broose_load_tables(self._h, C.byref(self._bp), _ptr(ids), len(ids), _ptr(xy), _ptr(off),
+                                                 _ptr(nd) if len(nd) else None, 0), "ovs_broose_load_tables")
+        self.n, self.overlay = len(ids), OVERLAY_BROOSE
+
+    def broose_export(self):
+        """(row_off (n * rows + 1), row_nodes) of the loaded Broose buckets."""
+        off = np.empty(self.n * self._bp.num_rows() + 1, dtype=np.uint64)
+        tot = C.c_uint64(0)
+        self._chk(self._L.ovs_broose_export(self._h, _ptr(off), None, 0, C.byref(tot)), "ovs_broose_export")
+        nodes = np.empty(max(int(tot.value), 1), dtype=np.uint32)
+        self._chk(self._L.ovs_broose_export(self._h, _ptr(off), _ptr(nodes), len(nodes), C.byref(tot)), "ovs_broose_export")
+        return off, nodes[:int(tot.value)]
+
+    def broose_find_node(self, node, keys, right, ext=None, numRedundantNodes: int = 1, numSiblings: int = 1,
+                         max_out: int | None = None):
+        """Broose::findNode at node[i] for keys[i] (ovs_broose_find_node_batch).  ext = BROOSE_EXT_DTYPE records
+        (None: calls without an extension); right[i] = the direction of an extension created in call i.
+        Returns (nodes (n, max_out) NONE padded, count, sibling flag, status (1 = the reference errors),
+        the extensions the responses carry)."""
+        node = np.ascontiguousarray(node, dtype=np.uint32)
+        keys = keys_array(keys)
+        n = len(node)
+        right = np.ascontiguousarray(np.broadcast_to(right, (n,)), dtype=np.uint8)
+        ext = np.zeros(n, dtype=BROOSE_EXT_DTYPE) if ext is None else np.ascontiguousarray(ext, dtype=BROOSE_EXT_DTYPE).copy()
+        mo = max_out or max(numRedundantNodes, numSiblings, 1)
+        out = np.empty((n, mo), dtype=np.uint32)
+        cnt = np.empty(n, dtype=np.uint8)
+        sib = np.empty(n, dtype=np.uint8)
+        st = np.empty(n, dtype=np.uint8)
+        self._chk(self._L.ovs_broose_find_node_batch(self._h, _ptr(node), _ptr(keys), _ptr(ext), _ptr(right), n,
+                                                     numRedundantNodes, numSiblings, _ptr(out), mo, _ptr(cnt), _ptr(sib),
+                                                     _ptr(st)), "ovs_broose_find_node_batch")
+        return out, cnt, sib, st, ext
+
+    def broose_directions(self, keys, src, parity=None):
+        """The per-lookup direction flags Broose's chooseLookup++ (Broose.cc:643) gives a batch that runs in
+        order: a lookup turns right iff its source created an odd number of extensions before it, and a
+        lookup creates one unless its source is a sibling of its key.  parity: chooseLookup per node before
+        the batch (None: 0).  Returns (right flags uint8, chooseLookup per node after the batch)."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        par = np.zeros(self.n, dtype=np.int64) if parity is None else np.array(parity, dtype=np.int64)
+        if len(src) == 0:
+            return np.zeros(0, dtype=np.uint8), par
+        _, _, sib, _, _ = self.broose_find_node(src, keys, 0)
+        creates = (sib == 0).astype(np.int64)
+        order = np.argsort(src, kind="stable")
+        s, cr = src[order], creates[order]
+        csum = np.cumsum(cr) - cr                           # extensions created before, over the sorted batch
+        first = np.r_[0, np.flatnonzero(s[1:] != s[:-1]) + 1]
+        before = csum - np.repeat(csum[first], np.diff(np.r_[first, len(s)]))
+        right = np.empty(len(src), dtype=np.uint8)
+        right[order] = ((par[s] + before) % 2).astype(np.uint8)
+        np.add.at(par, src, creates)
+        return right, par
+
+    def broose_lookup(self, keys, src, right, record_hops: bool = False, count_rpcs: bool = False) -> dict:
+        """Batched KBRTestApp one-way lookups on a Broose context (ovs_broose_route_batch); right[i] = lookup
+        i's direction flag (broose_directions).  Returns numpy arrays by field, as lookup()."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        right = np.ascontiguousarray(np.broadcast_to(right, (n,)), dtype=np.uint8)
+        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
+        H = max(self.get_params().hopCountMax, 1)
+        hop = np.empty((n, H), dtype=np.uint32) if record_hops else None
+        rpcs = np.empty(n, dtype=np.uint32) if count_rpcs else None
+        self._chk(self._L.ovs_broose_route_batch(self._h, _ptr(keys), _ptr(src), _ptr(right), n, _ptr(out), _ptr(hop),
+                                                 _ptr(rpcs), 0, None), "ovs_broose_route_batch")
+        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
+        if hop is not None:
+            res["hop_seq"] = hop
+        if rpcs is not None:
+            res["rpcs"] = rpcs
+        return res
+
+    def broose_lookup_device(self, keys_ptr: int, src_ptr: int, right_ptr: int, n: int, out_ptr: int,
+                             stream: int | None = None, rpcs_ptr: int | None = None):
+        """Device-resident batch (async on `stream`)."""
+        self._chk(self._L.ovs_broose_route_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), C.c_void_p(right_ptr), n,
+                                                 C.c_void_p(out_ptr), None, C.c_void_p(rpcs_ptr) if rpcs_ptr else None,
+                                                 DEVICE_PTRS, C.c_void_p(stream) if stream else None),
+                  "ovs_broose_route_batch")
 
     def epichord_load(self, ids, xy, succ, nsucc, pred, npred, lists_full, cache_off, cache_node, cache_last_ns,
                       cache_ttl_ns):

@@ -1,0 +1,112 @@
+"""Shared inputs of the Broose tests: networks with their model (built once per parameter set and shared), and
+findNode calls of every class the GPU test must cover, constructed and classified by the model."""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from oversim_amd import workload as W
+from oversim_amd.kbr import BROOSE_EXT_DTYPE, key_from_int
+import refmodel_broose as RB
+
+NONE = 0xFFFFFFFF
+FIELDS = ("responsible", "hops", "status", "one_way_hops", "latency_ns")
+
+
+@functools.lru_cache(maxsize=None)
+def network(n: int, seed: int = 41):
+    return W.population(n, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def model(n: int, sb: int = 2, user_dist: int = 0, rnd: bool = True, seed: int = 41) -> RB.BrooseNet:
+    net = network(n, seed)
+    return RB.BrooseNet(net.ids, net.xy, shifting_bits=sb, user_dist=user_dist, rnd=rnd)
+
+
+def with_rounding(m: RB.BrooseNet, rnd: bool) -> RB.BrooseNet:
+    """the same tables under the other SimTime rounding rule (the tables do not depend on it)"""
+    c = RB.BrooseNet.__new__(RB.BrooseNet)
+    c.__dict__.update(m.__dict__)
+    c.rnd = rnd
+    return c
+
+
+def ext_record(e: RB.Ext | None):
+    r = np.zeros((), dtype=BROOSE_EXT_DTYPE)
+    if e is not None:
+        r["route_key"] = key_from_int(e.route_key)
+        r["step"], r["has_ext"], r["right_shifting"], r["last_node"] = e.step, 1, int(e.right), e.last_node
+    return r
+
+
+def model_routes(m: RB.BrooseNet, keys, src, right, **kw):
+    res = [m.lookup(keys[i], int(src[i]), bool(right[i]), **kw) for i in range(len(keys))]
+    out = {f: np.array([r[f] for r in res], dtype=np.int64) for f in FIELDS + ("rpcs", "find_nodes")}
+    out["hop_seq"] = [r["hop_seq"] for r in res]
+    return out
+
+
+def assert_routes_equal(got: dict, want: dict, H: int):
+    for f in FIELDS:
+        g = got[f].astype(np.int64)
+        w = want[f] if f != "responsible" else want[f] & 0xFFFFFFFF
+        bad = np.flatnonzero(g != w)
+        assert bad.size == 0, (f, bad[:5], g[bad[:5]], w[bad[:5]])
+    if "rpcs" in got:
+        assert np.array_equal(got["rpcs"].astype(np.int64), want["rpcs"])
+    if "hop_seq" in got:
+        for i, seq in enumerate(want["hop_seq"]):
+            row = got["hop_seq"][i]
+            assert list(row[:len(seq)]) == seq and np.all(row[len(seq):] == NONE), i
+
+
+def find_node_calls(m: RB.BrooseNet, total: int, seed: int):
+    """`total` findNode calls (node, key, incoming extension or None, direction flag) with their class names:
+    sibling, first_left, first_right, mid_left, mid_right, brother, loop, broken -- the mid-route and brother
+    calls are the ones the model's own lookups send."""
+    rng = np.random.default_rng(seed)
+    calls = []
+
+    def add(v, k, e, right):
+        msg = {} if e is None else {"ext": e.copy()}
+        cnt = [0]
+        try:
+            res = m.find_node(v, k, 1, 1, msg, right, cnt)
+        except RB.BrooseError:
+            calls.append((v, k, e, right, "broken", None, None))
+            return None
+        sib = m.is_sibling_for(v, k, 1)
+        if sib:
+            cls = "sibling"
+        elif cnt[0] > 1:
+            cls = "loop"
+        elif e is None:
+            cls = "first_right" if right else "first_left"
+        elif e.step == 0:
+            cls = "brother"
+        else:
+            cls = "mid_right" if e.right else "mid_left"
+        calls.append((v, k, e, right, cls, res, msg.get("ext")))
+        return None if sib else (res[0], msg["ext"])
+
+    while len(calls) < total - 200:
+        # one chain: the calls of a lookup, each fed the extension the previous response carried
+        k = RB.to_int(W.random_keys(1, rng)[0])
+        v, e, right = int(rng.integers(0, m.n)), None, bool(rng.integers(0, 2))
+        for _ in range(40):
+            nxt = add(v, k, e, right)
+            if nxt is None or nxt[0] == v:
+                break
+            v, e = nxt[0], nxt[1]
+    # calls whose first answer is the node itself, a broken one (a step that reads bit 160), exact keys
+    import test_broose_model as T
+    while len(calls) < total - 20:
+        v = int(rng.integers(0, m.n))
+        k, e = T.loop_call(m, v, m.sb * int(rng.integers(2, 8)))
+        add(v, k, e, False)
+    while len(calls) < total:
+        v = int(rng.integers(0, m.n))
+        add(v, m.ids[v] ^ (1 << 158), None, False if m.user_dist == 0 else True)
+    return calls[:total]

@@ -1,0 +1,221 @@
+"""The Broose model (tests/refmodel_broose.py) checked on the CPU: the snapshot that BrooseBucket::add builds from
+every node in a shuffled order against brute force (sort all nodes by XOR to the bucket key, take maxSize) and
+against the trie descent the GPU tests build their networks with; the fixed point (addNode of any network node
+changes no bucket); keyInRange, longestPrefix, the distance estimate's rounding and clamp; both directions of
+findNode, the end of its self-recursion, and whole routes.  Also the host-side validation of explicit tables as a
+stand-alone program under the sanitizers."""
+from __future__ import annotations
+
+import random
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from oversim_amd import workload as W
+import refmodel_broose as RB
+from refmodel_broose import BrooseBucket, BrooseError, BrooseNet, Ext, closest_brute, closest_fast
+
+ROOT = Path(__file__).resolve().parent.parent
+SIZES = [2, 3, 9, 64, 1000]
+
+
+def _sample(n, cnt=24, seed=5):
+    return list(range(n)) if n <= 64 else sorted(random.Random(seed).sample(range(n), cnt))
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("sb", [1, 2, 3])
+def test_snapshot_is_brute_force_and_a_fixed_point(n, sb):
+    net = W.population(n, 31)
+    nodes = _sample(n, 12 if sb != 2 else 24)
+    a = BrooseNet(net.ids, net.xy, shifting_bits=sb, build="add", nodes=nodes, seed=n + sb)
+    b = BrooseNet(net.ids, net.xy, shifting_bits=sb, build="add", nodes=nodes, seed=1000 + n)      # another order
+    f = BrooseNet(net.ids, net.xy, shifting_bits=sb, build="fast", nodes=nodes)
+    for v in nodes:
+        want = [closest_brute(a.ids, bk.key, bk.max_size) for bk in a.buckets[v]]
+        assert a.rows(v) == want, (v, "add order 1")
+        assert b.rows(v) == want, (v, "add order 2")
+        assert f.rows(v) == want, (v, "trie descent")
+        assert v in a.b_bucket(v).nodes()                   # the own handle: distance 0 in the bBucket
+        # the fixed point: addNode (Broose.cc:1116-1122) of any node of the network changes nothing
+        for j in (range(n) if n <= 64 else random.Random(v).sample(range(n), 40)):
+            assert not a.add_node(a.buckets[v], j), (v, j)
+
+
+def test_closest_fast_on_adversarial_ids():
+    ids = sorted({0, 1, 2, 3, 1 << 159, (1 << 159) + 1, (1 << 160) - 1, 5 << 100, (5 << 100) + 7, 1 << 80})
+    for t in ids + [0x1234 << 90, (1 << 160) - 2, 6]:
+        for m in (1, 2, 5, 20):
+            assert closest_fast(ids, t, m) == closest_brute(ids, t, m)
+
+
+def test_bucket_keys():
+    me = (0b1011 << 156) | 0x55
+    r3 = BrooseBucket(me, 2, 3, 8)
+    assert r3.key == (me >> 2) + (3 << 158)
+    assert BrooseBucket(me, 2, 0, 8).key == me >> 2
+    assert BrooseBucket(me, -2, 0, 32).key == (me << 2) % RB.M
+    assert BrooseBucket(me, 0, 0, 56, True).key == me
+
+
+def test_longest_prefix_0_1_2_entries():
+    ids = [0b1010 << 156, 0b1011 << 156, 0b0011 << 156]
+    b = BrooseBucket(ids[0], 0, 0, 8)
+    assert b.longest_prefix(ids) == 0
+    b.add(0, ids[0])
+    assert b.longest_prefix(ids) == 0
+    b.add(1, ids[1])
+    assert b.longest_prefix(ids) == 3
+    b.add(2, ids[2])
+    assert b.longest_prefix(ids) == 0
+
+
+def test_key_in_range_three_branches():
+    me = 1 << 100
+    ids = [me ^ (i * i + i) for i in range(80)]         # distinct distances to me
+    b = BrooseBucket(me, 0, 0, 56, is_b=True)
+    assert not b.key_in_range(me)                        # empty
+    for j in range(8):
+        b.add(j, ids[j])
+    assert b.key_in_range(0) and b.key_in_range(RB.M - 1)   # size <= maxSize / 7
+    for j in range(8, 80):
+        b.add(j, ids[j])
+    assert len(b.dist) == 56
+    d = b.dist[56 // 7 - 1]
+    assert b.key_in_range(me ^ d) and not b.key_in_range(me ^ (d + 1)) and b.key_in_range(me)
+    r = BrooseBucket(me, 2, 0, 4)                        # not a bBucket: the last entry's distance
+    for j in range(6):
+        r.add(j, ids[j])
+    assert r.key_in_range(me ^ r.dist[-1]) and not r.key_in_range(me ^ (r.dist[-1] + 1))
+
+
+@pytest.mark.parametrize("sb", [1, 2, 3, 7])
+@pytest.mark.parametrize("user_dist", [0, 4])
+def test_distance_estimate_rounding_and_clamp(sb, user_dist):
+    net = W.population(64, 32)
+    m = BrooseNet(net.ids, net.xy, shifting_bits=sb, user_dist=user_dist, r_bucket_size=2, nodes=[0, 1, 2])
+    for v in (0, 1, 2):
+        raw = max(m.r_bucket(v, 0).longest_prefix(m.ids), m.r_bucket(v, 1).longest_prefix(m.ids)) + 1 + user_dist
+        d = m.distance_estimate(v)
+        assert d % sb == 0 and raw <= d < raw + sb
+    # the clamp: longestPrefix of two equal-prefix entries pushed to the key length
+    big = BrooseNet(net.ids, net.xy, shifting_bits=sb, user_dist=200, nodes=[0])
+    assert big.distance_estimate(0) == 160 - 160 % sb
+    assert big.distance_estimate(0) % sb == 0 and big.distance_estimate(0) <= 160
+
+
+@pytest.fixture(scope="module")
+def net1000():
+    net = W.population(1000, 33)
+    return net, BrooseNet(net.ids, net.xy)
+
+
+def test_find_node_both_directions_and_loop_end(net1000):
+    net, m = net1000
+    rng = np.random.default_rng(34)
+    keys = [RB.to_int(k) for k in W.random_keys(300, rng)]
+    loops = 0
+    for i, k in enumerate(keys):
+        v = int(rng.integers(0, m.n))
+        for right in (False, True):
+            msg, cnt = {}, [0]
+            res = m.find_node(v, k, 8, 1, msg, right, cnt)
+            if m.is_sibling_for(v, k, 1):
+                assert "ext" not in msg and len(res) == 1
+                continue
+            e = msg["ext"]
+            assert e.right == right and e.step % m.sb == 0 and e.last_node == v
+            assert (e.step >= 0) if right else (e.step <= 0)
+            d = m.distance_estimate(v)
+            # the rounds the call took: one step of shiftingBits each, the brother lookup at step 0 moves nothing
+            moved = (d - e.step) if right else (e.step + d)
+            assert moved == m.sb * cnt[0] or (moved == m.sb * (cnt[0] - 1) and e.step == 0)
+            assert cnt[0] <= d // m.sb + 1                  # the self-recursion ends
+            loops += cnt[0] > 1
+            assert res[0] != v or e.step == 0
+            if right:
+                # the key's bits from 160 - d upwards shifted in from the left, self's top bits below them
+                assert e.route_key == (((k >> (160 - d)) & ((1 << moved) - 1)) << (160 - moved)) + (m.ids[v] >> moved)
+            else:
+                assert e.route_key == (((m.ids[v] >> (160 - d)) << (160 - d)) + (k >> d)) << moved & (RB.M - 1)
+    # first calls from random nodes seldom answer with the node itself; calls that must: a right-shifting
+    # extension whose next route key is the responder's own key (loop_call)
+    for v in range(0, m.n, 37):
+        k, e = loop_call(m, v, 6 * m.sb)
+        if m.is_sibling_for(v, k, 1):
+            continue
+        msg, cnt = {"ext": e}, [0]
+        res = m.find_node(v, k, 1, 1, msg, None, cnt)
+        assert cnt[0] > 1 and cnt[0] <= 6 + 1 and (res[0] != v or msg["ext"].step == 0)
+        loops += 1
+    assert loops > 0
+
+
+def loop_call(m, v, step):
+    """(key, extension) of a right-shifting call at v whose first round lands the route key on v's own key, so
+    that findNode answers with v itself and runs again (Broose.cc:765-768)"""
+    me = m.ids[v]
+    top = me >> (160 - m.sb)
+    k = (me ^ (1 << 159)) & ~(((1 << m.sb) - 1) << (160 - step)) | (top << (160 - step))
+    return k, Ext((me << m.sb) % RB.M, step, True, v)
+
+
+def test_find_node_errors():
+    net = W.population(64, 35)
+    m = BrooseNet(net.ids, net.xy, user_dist=40)            # distance estimates above 31
+    k = (m.ids[5] + (1 << 158)) % RB.M
+    assert not m.is_sibling_for(5, k, 1)
+    with pytest.raises(BrooseError):
+        m.find_node(5, k, 1, 1, {}, right=False)
+    assert m.find_node(5, k, 1, 1, {}, right=True)           # right shifting has no such limit
+    with pytest.raises(BrooseError):                          # a right-shifting step below shiftingBits reads bit 160
+        m.find_node(5, k, 1, 1, {"ext": Ext(m.ids[5], 1, True, 5)})
+    with pytest.raises(BrooseError):
+        m.find_node(5, k, 1, 1, {"ext": Ext(m.ids[5], 2, False, 5)})
+    with pytest.raises(BrooseError):
+        m.is_sibling_for(5, k, 9)
+    assert m.is_sibling_for(5, m.ids[5], 0) and not m.is_sibling_for(5, k, 0)
+
+
+def test_routes_deliver_in_both_directions(net1000, capsys):
+    net, m = net1000
+    rng = np.random.default_rng(36)
+    nq = 1500
+    keys = W.random_keys(nq, rng)
+    src = rng.integers(0, m.n, nq)
+    closest = [closest_fast(m.ids, RB.to_int(k), 1)[0] for k in keys]
+    for right in (False, True):
+        res = [m.lookup(keys[i], int(src[i]), right) for i in range(nq)]
+        ok = sum(r["status"] == 0 for r in res)
+        exact = sum(r["status"] == 0 and r["responsible"] == closest[i] for i, r in enumerate(res))
+        hops = np.mean([r["hops"] for r in res])
+        fns = np.mean([r["find_nodes"] for r in res])
+        with capsys.disabled():
+            print(f"\nbroose n=1000 right={right}: delivered {ok}/{nq}, at the XOR-closest node {exact}/{nq} "
+                  f"({100.0 * exact / nq:.2f} %), mean hops {hops:.3f}, findNodes per lookup {fns:.3f}")
+        # the shares delivered and delivered at the globally closest node are measured, not claimed:
+        # neither is 100 % in the model.  What holds for every lookup: with no timeouts a route either arrives or
+        # ends at an already visited next hop, after one FindNodeCall per hop and no responder twice
+        assert ok > 0 and all(r["status"] in (0, 4) for r in res)
+        for r in res:
+            assert r["rpcs"] == r["hops"] and len(r["hop_seq"]) == r["hops"]
+            assert len(set(r["hop_seq"])) == r["hops"]        # visitOnlyOnce
+
+
+def test_directions_helper():
+    flags, par = RB.directions([3, 3, 4, 3, 3], [True, False, True, True, True])
+    assert flags == [False, True, False, True, False] and par == {3: 3, 4: 1}
+
+
+def test_table_validation_driver(tmp_path):
+    """tests/broose_tables_driver.cpp: broose_validate_tables (what ovs_broose_load_tables runs on the host) on
+    malformed CSR input, as a stand-alone program built with -fsanitize=address,undefined."""
+    exe = tmp_path / "broose_tables_driver"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", str(ROOT / "include"), "-I", str(ROOT / "oversim_amd" / "csrc"),
+                    str(ROOT / "tests" / "broose_tables_driver.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ok" in r.stdout
