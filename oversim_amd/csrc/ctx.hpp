@@ -1,11 +1,13 @@
 // ctx.hpp -- the context and the host helpers its entry points share (internal).
 //
-// The translation units that implement the C ABI include this: ovs_kbr.cpp (context, loaders, route,
-// lookup, refresh, maintenance, shard steps) and the application tiers app_*.cpp.  The tiers reach the
-// router through route_check / route_device and lookup_check / lookup_device, never through the public
-// entry points: one argument check, one hipSetDevice and one CallFrame per call.  Nothing writes
-// c->P but ovs_set_params and the loaders; a tier that routes under another message length passes a
-// copy.  shard_route.cpp drives a context through the public ABI and sees ctx_internal.hpp only.
+// The translation units that implement the C ABI include this: ovs_ctx.cpp (the context, its parameters,
+// what every call shares), ovs_load.cpp (loaders, exports, Chord maintenance rounds; ovs_broose.cpp: Broose's),
+// ovs_shard.cpp (shard steps), ovs_route.cpp (the route / lookup / findNode seam), ovs_kad_maint.cpp (Kademlia
+// refresh and maintenance) and the application tiers app_*.cpp; host_checks.hpp holds the refusals on plain
+// values.  The tiers reach the router through route_check / route_device and lookup_check / lookup_device,
+// never through the public entry points: one argument check, one hipSetDevice and one CallFrame per call.
+// Nothing writes c->P but ovs_set_params and the loaders; a tier that routes under another message length
+// passes a copy.  shard_route.cpp drives a context through the public ABI and sees ctx_internal.hpp only.
 #pragma once
 #include <map>
 #include <vector>
@@ -15,6 +17,7 @@
 #include "ctx_internal.hpp"
 #include "dht.hpp"
 #include "epichord.hpp"
+#include "host_checks.hpp"
 #include "host_tables.hpp"
 #include "kad.hpp"
 #include "kad_shard.hpp"
@@ -118,6 +121,10 @@ ovs_status lease_fail(ovs_ctx* c, const char* name, const CachedBuf::Lease& L);
 int64_t simtime_host(double seconds, int round);
 int32_t route_bytes(const ovs_params& P);
 DelayConsts delay_consts(const ovs_params& P);
+// the response of a converged n-node ring's LookupCall there and back: min(ns, 1 + successors) NodeHandles
+int64_t ring_sibling_response_ns(const DelayConsts& DC, const ovs_params& P, uint64_t n, int ns);
+// a zeroed work counter for one launch of a persistent route kernel, or none (static slices only)
+DynSlots::Lease dyn_acquire(ovs_ctx* c, uint64_t n, hipStream_t s);
 
 // ---- refusals ----
 ovs_status check_common(ovs_ctx* c, const ovs_params& P);
@@ -126,12 +133,28 @@ ovs_status check_chord_route(ovs_ctx* c, const ovs_params& P);
 // be read out of bounds by the lookup kernels); device-pointer calls leave that to the caller (ovs_kbr.h)
 ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev);
 
-// ---- the loaders' common steps (ovs_broose.cpp loads through them too) ----
+// ---- the loaders' common steps ----
 // drop the loaded network and everything built on it
 void free_tables(ovs_ctx* c);
 void free_kad_shard(ovs_ctx* c);
+// One load: selects the device, drops the loaded network and the shard state, and refuses a context whose
+// params.overlay is not `overlay`.  A loader returns st unless that is OVS_OK, and commit() at its end;
+// every other way out drops what the load had built.  Only commit() sets c->overlay.
+struct LoadFrame {
+    LoadFrame(ovs_ctx* c, int overlay, const char* name);
+    ~LoadFrame() { if (live) free_tables(c); }
+    ovs_status commit() { c->overlay = overlay; live = false; return OVS_OK; }
+    ovs_ctx* c;
+    int overlay;
+    ovs_status st = OVS_OK;
+    bool live = false;      // the device is selected and the load has not committed
+};
 // sorted ids (+ coordinates) into c->recs / c->xy; OVS_EINVAL unless ascending and unique
 ovs_status upload_nodes(ovs_ctx* c, const ovs_key160* ids, uint64_t n, const double* xy, bool dev);
+// k-stride Kademlia tables of c->n nodes, on the host, staged and built into T.  *staged = false: no staging
+// buffers; hipErrorInvalidValue with bad[1] set: code bad[1] at node bad[0].  What either means is the caller's.
+hipError_t kad_build_from_host(ovs_ctx* c, const uint32_t* siblings, const uint8_t* bucket_count,
+                               const uint32_t* bucket_nodes, KadTables& T, bool* staged, uint32_t bad[2]);
 
 // ---- the loaded ring ----
 // NodeRec array of an ideal ring for the context's successorListSize (rebuilt when it changes)

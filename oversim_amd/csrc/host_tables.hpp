@@ -1,6 +1,6 @@
 // host_tables.hpp -- the host-side table bookkeeping of the C ABI (no HIP): explicit Chord tables
 // and the batched maintenance rounds' updates of them, and the validation / ordering of an
-// EpiChord snapshot.  ovs_kbr.cpp uploads what these produce; tests/test_sanitizers.py builds this
+// EpiChord snapshot.  ovs_load.cpp uploads what these produce; tests/test_sanitizers.py builds this
 // translation unit with plain g++ under ASan/UBSan and drives it (tests/host_tables_driver.cpp).
 #pragma once
 #include <stdint.h>

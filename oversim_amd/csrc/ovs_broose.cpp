@@ -6,7 +6,6 @@
 #include <vector>
 
 #include "ctx.hpp"
-#include "persist.hpp"
 
 using namespace ovs;
 
@@ -41,21 +40,16 @@ DelayConsts broose_delay_consts(const ovs_params& P)
     return d;
 }
 
+// what both loaders check between the frame's drop and the upload; the frame (ctx.hpp) does the rest
 ovs_status load_begin(ovs_ctx* c, const ovs_broose_params* bp, const ovs_key160* ids, uint64_t n, const double* xy, bool dev,
                       BrooseShape* sh)
 {
-    HIPCHK(c, hipSetDevice(c->device));
-    free_tables(c);
-    free_kad_shard(c);
-    if (c->P.overlay != OVS_OVERLAY_BROOSE) return fail(c, OVS_ESTATE, "params.overlay is not Broose");
     *sh = shape_of(*bp);
     std::string err;
     if (!broose_shape_ok(*sh, &err)) return fail(c, OVS_ENOTSUP, "Broose: " + err);
     if (n < 2) return fail(c, OVS_EINVAL, "Broose needs at least 2 nodes");
     if (n * (uint64_t)sh->stride() >= 0xFFFFFFFFull * 16) return fail(c, OVS_EINVAL, "too many nodes for the bucket rows");
-    const ovs_status s = upload_nodes(c, ids, n, xy, dev);
-    if (s != OVS_OK) free_tables(c);
-    return s;
+    return upload_nodes(c, ids, n, xy, dev);
 }
 
 }  // namespace
@@ -89,13 +83,13 @@ ovs_status ovs_broose_load(ovs_ctx* c, const ovs_broose_params* bp, const ovs_ke
                            uint32_t flags)
 {
     if (!c || !bp || !ids || !xy) return OVS_EINVAL;
+    LoadFrame L(c, OVS_OVERLAY_BROOSE, "Broose");
+    if (L.st) return L.st;
     BrooseShape sh;
-    const ovs_status s = load_begin(c, bp, ids, n, xy, flags & OVS_DEVICE_PTRS, &sh);
-    if (s != OVS_OK) return s;
+    if (ovs_status s = load_begin(c, bp, ids, n, xy, flags & OVS_DEVICE_PTRS, &sh)) return s;
     const hipError_t e = broose_build(c->recs, c->xy, (uint32_t)n, sh, c->broose, c->stream);
-    if (e != hipSuccess) { free_tables(c); return hip_fail(c, e, "broose snapshot build"); }
-    c->overlay = OVS_OVERLAY_BROOSE;
-    return OVS_OK;
+    if (e != hipSuccess) return hip_fail(c, e, "broose snapshot build");
+    return L.commit();
 }
 
 ovs_status ovs_broose_load_tables(ovs_ctx* c, const ovs_broose_params* bp, const ovs_key160* ids, uint64_t n, const double* xy,
@@ -114,19 +108,19 @@ ovs_status ovs_broose_load_tables(ovs_ctx* c, const ovs_broose_params* bp, const
         if (!broose_validate_tables(reinterpret_cast<const K160*>(ids), n, sh, row_off, row_nodes, &err))
             return fail(c, OVS_EINVAL, "Broose tables: " + err);
     }
+    LoadFrame L(c, OVS_OVERLAY_BROOSE, "Broose");
+    if (L.st) return L.st;
     BrooseShape sh;
-    const ovs_status s = load_begin(c, bp, ids, n, xy, false, &sh);
-    if (s != OVS_OK) return s;
+    if (ovs_status s = load_begin(c, bp, ids, n, xy, false, &sh)) return s;
     const uint64_t nr = n * (uint64_t)sh.nrows(), total = row_off[nr];
     CallFrame F(false, c->stream);
     const uint64_t* doff = F.in(row_off, nr + 1);
     const uint32_t* dn = F.in(row_nodes, total);
-    if (!F.ok()) { free_tables(c); return frame_fail(c, F); }
+    if (!F.ok()) return frame_fail(c, F);
     const hipError_t e = broose_build_from_csr(c->recs, c->xy, (uint32_t)n, sh, doff, dn, c->broose, c->stream);
-    if (e != hipSuccess) { free_tables(c); return hip_fail(c, e, "broose table upload"); }
-    if (F.finish() != hipSuccess) { free_tables(c); return frame_fail(c, F); }
-    c->overlay = OVS_OVERLAY_BROOSE;
-    return OVS_OK;
+    if (e != hipSuccess) return hip_fail(c, e, "broose table upload");
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
+    return L.commit();
 }
 
 ovs_status ovs_broose_export(ovs_ctx* c, uint64_t* row_off, uint32_t* row_nodes, uint64_t cap, uint64_t* total)
@@ -193,8 +187,7 @@ ovs_status ovs_broose_find_node_batch(ovs_ctx* c, const uint32_t* node, const ov
     const hipError_t e = broose_find_node(c->broose, dn, dk, de, dr, n, numRedundantNodes, numSiblings, dout, max_out, dc, dsib,
                                           dst, c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "broose findNode kernel");
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    return OVS_OK;
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
 }
 
 ovs_status ovs_broose_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, const uint8_t* right, uint64_t n,
@@ -215,8 +208,7 @@ ovs_status ovs_broose_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint
     const bool dev = flags & OVS_DEVICE_PTRS;
     hipStream_t s = dev ? (hipStream_t)stream : c->stream;
     if (n == 0) return OVS_OK;
-    st = check_sources(c, src, n, dev);
-    if (st != OVS_OK) return st;
+    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
     const uint64_t H = (uint64_t)P.hopCountMax;
     CallFrame F(dev, s);
     const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
@@ -236,14 +228,12 @@ ovs_status ovs_broose_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint
     } else {
         HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
     }
-    // small batches: static slices only (no memset, no event), as the other route kernels
-    const DynSlots::Lease dyn = persist_dyn_enabled() && n >= (1ull << 18) ? c->dyn.acquire(s) : DynSlots::Lease();
+    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
     const hipError_t e = broose_route(c->broose, broose_delay_consts(P), P.hopCountMax, dk, ds, dr, n, dout, dhop, drpc, c->num_cu, s,
                                       dyn.get());
     vis.release();
     if (e != hipSuccess) return hip_fail(c, e, "broose route kernel");
-    if (F.finish() != hipSuccess) return frame_fail(c, F);
-    return OVS_OK;
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
 }
 
 }  // extern "C"

@@ -177,7 +177,7 @@ void kernel(const uint32_t* a, const uint64_t* b, uint32_t* x, uint64_t* y, uint
     }
 }
 
-// one call as the entry points of ovs_kbr.cpp make it; *leases counts the leases it got
+// one call as the entry points of ovs_route.cpp make it; *leases counts the leases it got
 hipError_t call(bool dev, CachedBuf* cache, Arrays& h, int* leases)
 {
     CallFrame F(dev, S1);

@@ -165,3 +165,20 @@ def test_cstddev_clean_and_exact_under_asan_ubsan(tmp_path):
     assert got["one"] == (1, 2.5, 0.0, 2.5, 2.5)
     assert got["two"][:2] == (2, 2.5) and got["two"][2] == math.sqrt(4.5)
     assert got["sums"] == got["collect"], "from_sums over exact integer sums must equal collect() over the samples"
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_host_checks_clean_under_asan_ubsan(tmp_path):
+    """The entry points' refusals that depend on plain values only (oversim_amd/csrc/host_checks.hpp: the
+    shard steps' arc map, the shapes of Kademlia tables and routingBucketSize, the table builders' bad
+    codes, the refresh lookups' parameters, node-index ranges) built with plain g++ under ASan/UBSan
+    -Werror: every case's status and literal message (tests/host_checks_driver.cpp).  No HIP compiler and
+    no HIP library."""
+    exe = tmp_path / "host_checks_driver"
+    c = ["g++", "-std=c++17", *SAN, *WARN, "-I", str(ROOT / "oversim_amd" / "csrc"),
+         str(ROOT / "tests" / "host_checks_driver.cpp"), "-o", str(exe)]
+    r = subprocess.run(c, capture_output=True, text=True)
+    assert r.returncode == 0, f"{' '.join(c)}\n{r.stdout}{r.stderr}"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
