@@ -1282,6 +1282,66 @@ ovs_status  ovs_broose_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const u
                                    uint64_t n, ovs_route_out* out, uint32_t* hop_seq, uint32_t* rpcs, uint32_t flags,
                                    void* stream);
 
+/* ---- Pastry (src/overlay/pastry/; additive to ABI 12; test OVS_HAS_PASTRY) ----
+ * READY Pastry nodes with fixed tables: per node a leaf set of numberOfLeaves slots (PastryLeafSet.cc: the
+ * smaller keys in slots 0 .. L/2 - 1 with the predecessor last, the bigger keys from slot L/2 with the
+ * successor first) and a routing table of rows x 2^bitsPerDigit slots (PastryRoutingTable.cc).  A batch
+ * holds the tables fixed.  Implemented: BasePastry::findNode with both optimizeLookup and useRegularNextHop
+ * forms, and semi-recursive one-way routes (routingType 1, numSiblings 1, recNumRedundantNodes 1..8) without
+ * per-hop acks.  Refused with OVS_ENOTSUP: routeMsgAcks, numberOfNeighbors != 0, bitsPerDigit outside 1..4,
+ * odd numberOfLeaves or above 32, the other routing types.  Everything else on a Pastry context --
+ * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, every application tier -- is refused with
+ * OVS_ENOTSUP. */
+#define OVS_HAS_PASTRY 1
+enum { OVS_OVERLAY_PASTRY = 6 };
+typedef struct ovs_pastry_params {
+    int32_t bitsPerDigit;       /* **.pastry.bitsPerDigit = 4 (default.ini:226) */
+    int32_t numberOfLeaves;     /* **.pastry.numberOfLeaves = 16 (default.ini:227) */
+    int32_t numberOfNeighbors;  /* **.pastry.numberOfNeighbors = 0 (default.ini:228) */
+    int32_t optimizeLookup;     /* **.pastry.optimizeLookup = false (default.ini:234) */
+    int32_t useRegularNextHop;  /* **.pastry.useRegularNextHop = true (default.ini:236) */
+    int32_t routeMsgAcks;       /* **.pastry.routeMsgAcks = true (default.ini:245): refused at the route; set 0 */
+} ovs_pastry_params;
+void        ovs_pastry_params_default(ovs_pastry_params* out);
+/* Reads the **.overlay*.pastry.* keys above from ini text (config_name as for ovs_params_from_ini) into *bp,
+ * which holds the values to start from.  OVS_ENOTSUP naming the key where the ini sets a pastry key that
+ * would change a route and is not modelled: routingType other than "semi-recursive", or
+ * proximityNeighborSelection / enableNewLeafs / minimalJoinState / partialJoinPath / alwaysSendUpdate /
+ * useDiscovery / overrideOldPastry / overrideNewPastry set to anything but the value noted in DESIGN.md
+ * §9 (tables converged under them come in through ovs_pastry_load_tables). */
+ovs_status  ovs_pastry_params_from_ini(ovs_pastry_params* bp, const char* ini_text, const char* config_name, char* err,
+                                       int err_len);
+/* The converged tables, built on the device by the rule of DESIGN.md §4.  params.overlay must be
+ * OVS_OVERLAY_PASTRY. */
+ovs_status  ovs_pastry_load(ovs_ctx* ctx, const ovs_pastry_params* bp, const ovs_key160* ids_sorted, uint64_t n,
+                            const double* xy, uint32_t flags);
+/* routing-table rows of the loaded network (every node's rows beyond them are empty); -1 without one */
+int32_t     ovs_pastry_num_rows(const ovs_ctx* ctx);
+/* Explicit tables (host buffers) as node indices, 0xFFFFFFFF = unspecified: leaf[n][numberOfLeaves] in the
+ * reference's slot order, table[n][rows][2^bitsPerDigit], rows 1 .. 160 / bitsPerDigit.  Validated on the
+ * host: indices in [0, n); a leaf row holds neither its owner nor a node twice and is not empty; a table
+ * entry (r, c) shares exactly r digits with its owner and has digit c at r -- else OVS_EINVAL naming the
+ * node. */
+ovs_status  ovs_pastry_load_tables(ovs_ctx* ctx, const ovs_pastry_params* bp, const ovs_key160* ids_sorted, uint64_t n,
+                                   const double* xy, const uint32_t* leaf, const uint32_t* table, int32_t rows,
+                                   uint32_t flags);
+/* The loaded tables in the same form (host buffers): leaf[n][numberOfLeaves], table[n][ovs_pastry_num_rows][2^b]. */
+ovs_status  ovs_pastry_export(ovs_ctx* ctx, uint32_t* leaf, uint32_t* table);
+/* BasePastry::findNode (BasePastry.cc:1100-1211) at node[i] for keys[i] (host buffers).  numRedundantNodes
+ * 1..numberOfLeaves, numSiblings 0..numberOfLeaves/2.  out_nodes[i * max_out ..]: the answer in order,
+ * 0xFFFFFFFF padded, cut to max_out; out_count[i] its size; out_sibling[i] = isSiblingFor(node, key,
+ * numSiblings); out_status[i]: bit 0 = isSiblingFor's err (the NULL sibling vector, or this node not in
+ * it), bit 1 = the reference throws or dereferences a NULL vector (no answer then). */
+ovs_status  ovs_pastry_find_node_batch(ovs_ctx* ctx, const uint32_t* node, const ovs_key160* keys, uint64_t n,
+                                       int32_t numRedundantNodes, int32_t numSiblings, uint32_t* out_nodes,
+                                       uint32_t max_out, uint8_t* out_count, uint8_t* out_sibling, uint8_t* out_status);
+/* ovs_route_batch for a Pastry context: semi-recursive one-way routes (BaseOverlay.cc:1443-1582), reported
+ * as the Chord semi-recursive route reports them: OVS_LOOKUP_OK, OVS_LOOKUP_HOPMAX, OVS_LOOKUP_NO_NEXT (no
+ * useful next hop, or findNode returned nothing), OVS_LOOKUP_BROKEN where the reference throws.  out /
+ * hop_seq / flags / stream as for ovs_route_batch. */
+ovs_status  ovs_pastry_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                                   ovs_route_out* out, uint32_t* hop_seq, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,9 @@ from .kbr import DHT_ENTRY_DTYPE, DHT_EXPECT_DTYPE, DHT_GET_DTYPE, DHT_OP_DTYPE,
 from .kbr import DHT_TEAMS_REPEATED_HASHING, DHT_TEAMS_SYMMETRIC, DhtTeamParams  # noqa: F401
 from .kbr import SCRIBE_DELIVERY_DTYPE, SCRIBE_MSG_DTYPE, SCRIBE_NODE_DTYPE, SCRIBE_STATUS, ScribeParams  # noqa: F401
 from .kbr import BROOSE_EXT_DTYPE, OVERLAY_BROOSE, BrooseParams  # noqa: F401
+from .kbr import OVERLAY_PASTRY, PastryParams  # noqa: F401
 
-__all__ = ["BrooseParams", "BROOSE_EXT_DTYPE", "OVERLAY_BROOSE","KbrEngine", "KbrError", "Params", "Network", "lib", "keys_array", "key_from_int", "key_to_int",
+__all__ = ["PastryParams", "OVERLAY_PASTRY", "BrooseParams", "BROOSE_EXT_DTYPE", "OVERLAY_BROOSE","KbrEngine", "KbrError", "Params", "Network", "lib", "keys_array", "key_from_int", "key_to_int",
            "OVERLAY_CHORD", "OVERLAY_KADEMLIA", "ROUTE_OUT_DTYPE", "LOOKUP_OUT_DTYPE", "LOOKUP_STATUS", "NONE", "DEVICE_PTRS",
            "BCAST_NODE_DTYPE", "BcastStats", "RPC_OUT_DTYPE", "KbrTestRpcStats",
            "DhtParams", "DHT_OP_DTYPE", "DHT_PUT_DTYPE", "DHT_GET_DTYPE", "DHT_ENTRY_DTYPE", "DHT_EXPECT_DTYPE",

@@ -1,7 +1,7 @@
 // ctx.hpp -- the context and the host helpers its entry points share (internal).
 //
 // The translation units that implement the C ABI include this: ovs_ctx.cpp (the context, its parameters,
-// what every call shares), ovs_load.cpp (loaders, exports, Chord maintenance rounds; ovs_broose.cpp: Broose's),
+// what every call shares), ovs_load.cpp (loaders, exports, Chord maintenance rounds; ovs_broose.cpp: Broose's, ovs_pastry.cpp: Pastry's),
 // ovs_shard.cpp (shard steps), ovs_route.cpp (the route / lookup / findNode seam), ovs_kad_maint.cpp (Kademlia
 // refresh and maintenance) and the application tiers app_*.cpp; host_checks.hpp holds the refusals on plain
 // values.  The tiers reach the router through route_check / route_device and lookup_check / lookup_device,
@@ -23,6 +23,7 @@
 #include "kad_shard.hpp"
 #include "koorde.hpp"
 #include "launch.hpp"
+#include "pastry.hpp"
 #include "scribe.hpp"
 
 struct ovs_ctx {
@@ -67,6 +68,9 @@ struct ovs_ctx {
     ovs::EpiTables epi{};
     // broose buckets and records (ovs_broose_load / _load_tables; on the sorted ids in recs / xy)
     ovs::BrooseTables broose{};
+    // pastry leaf sets and routing tables (ovs_pastry_load / _load_tables; on the sorted ids in recs / xy)
+    ovs::PastryTables pastry{};
+    ovs_pastry_params pastry_bp{};
     ovs::CachedBuf kvis;                 // internal visited lists (K3 without hop_seq, K2x without responders)
     // K1's key-order buffers (ksort.hip): sorted keys, sources, caller indices and the sort's
     // histograms, one allocation shared by the calls on this context like kvis

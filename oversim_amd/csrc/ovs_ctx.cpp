@@ -55,6 +55,7 @@ void free_tables(ovs_ctx* c)
     koorde_free(c->koorde);
     epichord_free(c->epi);
     broose_free(c->broose);
+    pastry_free(c->pastry);
     for (CachedBuf* b : {&c->kvis, &c->ks, &c->bq, &c->rpcb, &c->dhtb, &c->scq}) b->free();
     if (c->dht.slots) hipFree(c->dht.slots);
     if (c->dht.hdr) hipFree(c->dht.hdr);

@@ -705,3 +705,57 @@ extern "C" void ovs_params_default(int32_t overlay, ovs_params* p)
         p->lookupMerge = 0;             // default.ini:428
     }
 }
+
+// **.overlay*.pastry.* (Pastry.ned / BasePastry.ned, default.ini:226-248).  Only what a route over fixed tables
+// reads is bound; a key that would change the tables or the route and is not modelled is refused when the ini
+// moves it off the value the fixed tables stand for.  The join, repair and maintenance timers do not touch a
+// READY node's routes and are ignored.
+extern "C" ovs_status ovs_pastry_params_from_ini(ovs_pastry_params* bp, const char* ini_text, const char* config_name,
+                                                 char* err, int err_len)
+{
+    auto set_err = [&](const std::string& m) {
+        if (err && err_len > 0) std::snprintf(err, (size_t)err_len, "%s", m.c_str());
+    };
+    if (!bp || !ini_text) { set_err("null argument"); return OVS_EINVAL; }
+    IniDoc doc;
+    {
+        std::string perr;
+        const ovs_status ps = doc.parse(ini_text, config_name, &perr);
+        if (ps != OVS_OK) { set_err(perr); return ps; }
+    }
+    const std::string pre = "SimpleUnderlayNetwork.overlayTerminal[0].overlay.pastry.";
+    std::string v;
+    struct IntKey { const char* name; int32_t* f; bool boolean; };
+    const IntKey keys[] = {{"bitsPerDigit", &bp->bitsPerDigit, false},       {"numberOfLeaves", &bp->numberOfLeaves, false},
+                           {"numberOfNeighbors", &bp->numberOfNeighbors, false}, {"optimizeLookup", &bp->optimizeLookup, true},
+                           {"useRegularNextHop", &bp->useRegularNextHop, true},  {"routeMsgAcks", &bp->routeMsgAcks, true}};
+    for (const IntKey& k : keys) {
+        if (!doc.lookup(pre + k.name, &v)) continue;
+        if (v.find("${") != std::string::npos) { set_err(std::string("pastry.") + k.name + " is a parameter study (${...})"); return OVS_ENOTSUP; }
+        if (!(k.boolean ? to_bool(unquote(v), k.f) : to_int(unquote(v), k.f))) {
+            set_err(std::string("pastry.") + k.name + ": cannot read \"" + v + "\"");
+            return OVS_EINVAL;
+        }
+    }
+    if (doc.lookup(pre + "routingType", &v) && unquote(v) != "semi-recursive") {
+        set_err("pastry.routingType = " + unquote(v) + " not supported: Pastry routes are semi-recursive");
+        return OVS_ENOTSUP;
+    }
+    // the values the fixed tables stand for: proximityNeighborSelection chooses among the candidates of a table
+    // slot by RTT (the converged-table rule does not; such tables come in through ovs_pastry_load_tables), the
+    // others change how a READY node's state moves while it routes
+    struct Fixed { const char* name; int32_t ok; };
+    const Fixed fixed[] = {{"proximityNeighborSelection", -1}, {"enableNewLeafs", 0},    {"minimalJoinState", 0},
+                           {"partialJoinPath", 0},             {"alwaysSendUpdate", 0},  {"useDiscovery", 0},
+                           {"overrideOldPastry", 0},           {"overrideNewPastry", 0}};
+    for (const Fixed& f : fixed) {
+        int32_t b = 0;
+        if (!doc.lookup(pre + f.name, &v)) continue;
+        if (!to_bool(unquote(v), &b)) { set_err(std::string("pastry.") + f.name + ": cannot read \"" + v + "\""); return OVS_EINVAL; }
+        if (f.ok >= 0 && b != f.ok) {
+            set_err(std::string("pastry.") + f.name + " = " + trim(v) + " not supported (DESIGN.md §9)");
+            return OVS_ENOTSUP;
+        }
+    }
+    return OVS_OK;
+}

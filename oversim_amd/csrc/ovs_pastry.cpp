@@ -1,0 +1,173 @@
+// ovs_pastry.cpp -- the Pastry entry points of the C ABI (include/ovs_kbr.h): the loaders, the export, the
+// findNode batch and the semi-recursive route.  The generic calls and the application tiers refuse a Pastry
+// context through refuse_dedicated (ovs_route.cpp).
+#include <string>
+#include <vector>
+
+#include "ctx.hpp"
+
+using namespace ovs;
+
+namespace {
+
+// what both loaders check between the frame's drop and the upload
+ovs_status load_begin(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_key160* ids, uint64_t n, const double* xy, bool dev)
+{
+    if (const char* why = pastry_shape_refusal(*bp)) return fail(c, OVS_ENOTSUP, why);
+    if (n < 2) return fail(c, OVS_EINVAL, "Pastry needs at least 2 nodes");
+    return upload_nodes(c, ids, n, xy, dev);
+}
+
+}  // namespace
+
+extern "C" {
+
+void ovs_pastry_params_default(ovs_pastry_params* p)
+{
+    if (!p) return;
+    p->bitsPerDigit = 4;        // default.ini:226
+    p->numberOfLeaves = 16;     // default.ini:227
+    p->numberOfNeighbors = 0;   // default.ini:228
+    p->optimizeLookup = 0;      // default.ini:234
+    p->useRegularNextHop = 1;   // default.ini:236
+    p->routeMsgAcks = 1;        // default.ini:245
+}
+
+int32_t ovs_pastry_num_rows(const ovs_ctx* c) { return c && c->overlay == OVS_OVERLAY_PASTRY ? c->pastry.rows : -1; }
+
+ovs_status ovs_pastry_load(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_key160* ids, uint64_t n, const double* xy,
+                           uint32_t flags)
+{
+    if (!c || !bp || !ids || !xy) return OVS_EINVAL;
+    // parameters outside the implemented ranges leave the loaded network as it is
+    if (const char* why = pastry_shape_refusal(*bp)) return fail(c, OVS_ENOTSUP, why);
+    LoadFrame L(c, OVS_OVERLAY_PASTRY, "Pastry");
+    if (L.st) return L.st;
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    if (ovs_status s = load_begin(c, bp, ids, n, xy, dev)) return s;
+    const PastryShape sh = pastry_shape_of(*bp);
+    if (n - 1 >= (uint64_t)sh.L) {
+        const hipError_t e = pastry_build(c->recs, c->xy, (uint32_t)n, sh, c->pastry, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "pastry table build");
+    } else {
+        // at most numberOfLeaves nodes: the leaf sets are the reference's own merge, replayed here
+        std::vector<K160> hid(n);
+        HIPCHK(c, hipMemcpy(hid.data(), ids, sizeof(K160) * n, dev ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+        std::vector<uint32_t> leaf(n * (uint64_t)sh.L);
+        for (uint32_t v = 0; v < (uint32_t)n; ++v) pastry_host_leaves(hid.data(), (uint32_t)n, sh.L, v, leaf.data() + (uint64_t)v * sh.L);
+        int rows = 0;
+        hipError_t e = pastry_rule_rows(c->recs, (uint32_t)n, sh.b, &rows, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "pastry row count");
+        CallFrame F(false, c->stream);
+        const uint32_t* dl = F.in(leaf.data(), leaf.size());
+        if (!F.ok()) return frame_fail(c, F);
+        e = pastry_build_explicit(c->recs, c->xy, (uint32_t)n, sh, rows, dl, nullptr, c->pastry, c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "pastry table build");
+        if (F.finish() != hipSuccess) return frame_fail(c, F);
+    }
+    c->pastry_bp = *bp;
+    return L.commit();
+}
+
+ovs_status ovs_pastry_load_tables(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_key160* ids, uint64_t n, const double* xy,
+                                  const uint32_t* leaf, const uint32_t* table, int32_t rows, uint32_t flags)
+{
+    if (!c || !bp || !ids || !xy || !leaf || !table) return OVS_EINVAL;
+    if (flags & OVS_DEVICE_PTRS) return fail(c, OVS_ENOTSUP, "ovs_pastry_load_tables takes host buffers");
+    if (const char* why = pastry_shape_refusal(*bp)) return fail(c, OVS_ENOTSUP, why);
+    const PastryShape sh = pastry_shape_of(*bp);
+    {
+        // the tables are checked before anything is dropped or uploaded
+        std::string err;
+        if (n < 2 || n >= 0xFFFFFFFFull) return fail(c, OVS_EINVAL, "node count out of range");
+        if (!pastry_validate_tables(reinterpret_cast<const K160*>(ids), n, sh, rows, leaf, table, &err))
+            return fail(c, OVS_EINVAL, "Pastry tables: " + err);
+    }
+    LoadFrame L(c, OVS_OVERLAY_PASTRY, "Pastry");
+    if (L.st) return L.st;
+    if (ovs_status s = load_begin(c, bp, ids, n, xy, false)) return s;
+    CallFrame F(false, c->stream);
+    const uint32_t* dl = F.in(leaf, n * (uint64_t)sh.L);
+    const uint32_t* dt = F.in(table, n * (uint64_t)rows * (uint64_t)sh.P());
+    if (!F.ok()) return frame_fail(c, F);
+    const hipError_t e = pastry_build_explicit(c->recs, c->xy, (uint32_t)n, sh, rows, dl, dt, c->pastry, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "pastry table upload");
+    if (F.finish() != hipSuccess) return frame_fail(c, F);
+    c->pastry_bp = *bp;
+    return L.commit();
+}
+
+ovs_status ovs_pastry_export(ovs_ctx* c, uint32_t* leaf, uint32_t* table)
+{
+    if (!c || !leaf || !table) return OVS_EINVAL;
+    if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    const PastryTables& t = c->pastry;
+    CallFrame F(false, c->stream);
+    uint32_t* dl = F.out(leaf, c->n * (uint64_t)t.sh.L);
+    uint32_t* dt = F.out(table, c->n * (uint64_t)t.rows * (uint64_t)t.sh.P());
+    if (!F.ok()) return frame_fail(c, F);
+    const hipError_t e = pastry_slot_nodes(t, dl, dt, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "pastry export");
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+}
+
+ovs_status ovs_pastry_find_node_batch(ovs_ctx* c, const uint32_t* node, const ovs_key160* keys, uint64_t n,
+                                      int32_t numRedundantNodes, int32_t numSiblings, uint32_t* out_nodes, uint32_t max_out,
+                                      uint8_t* out_count, uint8_t* out_sibling, uint8_t* out_status)
+{
+    if (!c || max_out == 0 || (n && (!node || !keys || !out_nodes || !out_count || !out_sibling || !out_status))) return OVS_EINVAL;
+    if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
+    const PastryShape& sh = c->pastry.sh;
+    // getMaxNumRedundantNodes / getMaxNumSiblings (BasePastry.cc:1090-1098, 1105-1110)
+    if (numRedundantNodes < 1 || numRedundantNodes > sh.L)
+        return fail(c, OVS_EINVAL, "numRedundantNodes must be 1..numberOfLeaves (getMaxNumRedundantNodes)");
+    if (numSiblings < 0 || numSiblings > sh.L / 2)
+        return fail(c, OVS_EINVAL, "numSiblings must be 0..numberOfLeaves/2 (getMaxNumSiblings)");
+    if (n == 0) return OVS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (uint64_t i = 0; i < n; ++i)
+        if (node[i] >= c->n) return fail(c, OVS_EINVAL, "node index out of range");
+    CallFrame F(false, c->stream);
+    const uint32_t* dn = F.in(node, n);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    uint32_t* dout = F.out(out_nodes, n * (uint64_t)max_out);
+    uint8_t* dc = F.out(out_count, n);
+    uint8_t* dsib = F.out(out_sibling, n);
+    uint8_t* dst = F.out(out_status, n);
+    if (!F.ok()) return frame_fail(c, F);
+    const hipError_t e = pastry_find_node(c->pastry, dn, dk, n, numRedundantNodes, numSiblings, dout, max_out, dc, dsib, dst, c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "pastry findNode kernel");
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+}
+
+ovs_status ovs_pastry_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_route_out* out,
+                                  uint32_t* hop_seq, uint32_t flags, void* stream)
+{
+    if (!c || (n && (!keys || !src || !out))) return OVS_EINVAL;
+    if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
+    const ovs_params& P = c->P;
+    ovs_status st = check_common(c, P);
+    if (st != OVS_OK) return st;
+    if (const char* why = pastry_route_refusal(P, c->pastry_bp)) return fail(c, OVS_ENOTSUP, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    if (n == 0) return OVS_OK;
+    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
+    const uint64_t H = (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
+    CallFrame F(dev, s);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dout = F.out(out, n);
+    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
+    if (dhop) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+    const hipError_t e = pastry_route(c->pastry, delay_consts(P), P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout, dhop,
+                                      c->num_cu, s, dyn.get());
+    if (e != hipSuccess) return hip_fail(c, e, "pastry route kernel");
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+}
+
+}  // extern "C"

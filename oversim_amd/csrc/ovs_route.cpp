@@ -123,6 +123,8 @@ static ovs_status refuse_dedicated(ovs_ctx* c, bool serves_koorde = false, const
         return fail(c, OVS_ENOTSUP, epichord ? epichord : "EpiChord: ovs_epichord_find_node_batch only");
     if (c->overlay == OVS_OVERLAY_BROOSE)
         return fail(c, OVS_ENOTSUP, "Broose: ovs_broose_route_batch and ovs_broose_find_node_batch only");
+    if (c->overlay == OVS_OVERLAY_PASTRY)
+        return fail(c, OVS_ENOTSUP, "Pastry: ovs_pastry_route_batch and ovs_pastry_find_node_batch only");
     return OVS_OK;
 }
 

@@ -36,6 +36,7 @@ OVERLAY_KADEMLIA = 2
 OVERLAY_KOORDE = 3
 OVERLAY_EPICHORD = 4
 OVERLAY_BROOSE = 5
+OVERLAY_PASTRY = 6
 DEVICE_PTRS = 0x1
 NONE = 0xFFFFFFFF
 
@@ -97,6 +98,12 @@ class Params(C.Structure):
     def broose(cls) -> "Params":
         """The overlay-independent parameters for a Broose context; Broose's own are BrooseParams."""
         return cls.default(OVERLAY_BROOSE)
+
+    @classmethod
+    def pastry(cls) -> "Params":
+        """The overlay-independent parameters for a Pastry context: Pastry's routingType is semi-recursive
+        (default.ini:246); Pastry's own parameters are PastryParams."""
+        return cls.default(OVERLAY_PASTRY).replace(routingType=1)
 
     @classmethod
     def from_ini(cls, text: str, config: str | None = None, overlay: int = OVERLAY_CHORD,
@@ -229,6 +236,36 @@ class BrooseParams(C.Structure):
 
     def row_cap(self, row: int) -> int:
         return int(lib().ovs_broose_row_cap(C.byref(self), row))
+
+
+class PastryParams(C.Structure):
+    """ovs_pastry_params: the **.pastry.* parameters a route over fixed tables reads (default.ini:226-245)."""
+
+    _fields_ = [("bitsPerDigit", C.c_int32), ("numberOfLeaves", C.c_int32), ("numberOfNeighbors", C.c_int32),
+                ("optimizeLookup", C.c_int32), ("useRegularNextHop", C.c_int32), ("routeMsgAcks", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw) -> "PastryParams":
+        """default.ini's values; routeMsgAcks = true among them is refused at the route, so callers pass
+        routeMsgAcks=0."""
+        p = cls()
+        lib().ovs_pastry_params_default(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+    @classmethod
+    def from_ini(cls, text: str, config: str | None = None, base: "PastryParams | None" = None) -> "PastryParams":
+        p = cls.default()
+        if base is not None:
+            C.memmove(C.byref(p), C.byref(base), C.sizeof(cls))
+        err = C.create_string_buffer(512)
+        st = lib().ovs_pastry_params_from_ini(C.byref(p), text.encode(), config.encode() if config else None, err, 512)
+        if st != 0:
+            raise KbrError(f"ovs_pastry_params_from_ini: {STATUS.get(st, st)}: {err.value.decode()}")
+        return p
 
 
 class DhtParams(C.Structure):
@@ -470,6 +507,14 @@ def lib() -> C.CDLL:
         "ovs_broose_export": ([vp, vp, vp, u64, C.POINTER(u64)], C.c_int),
         "ovs_broose_find_node_batch": ([vp, vp, vp, vp, vp, u64, i32, i32, vp, u32, vp, vp, vp], C.c_int),
         "ovs_broose_route_batch": ([vp, vp, vp, vp, u64, vp, vp, vp, u32, vp], C.c_int),
+        "ovs_pastry_params_default": ([vp], None),
+        "ovs_pastry_params_from_ini": ([vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int], C.c_int),
+        "ovs_pastry_load": ([vp, vp, vp, u64, vp, u32], C.c_int),
+        "ovs_pastry_num_rows": ([vp], i32),
+        "ovs_pastry_load_tables": ([vp, vp, vp, u64, vp, vp, vp, i32, u32], C.c_int),
+        "ovs_pastry_export": ([vp, vp, vp], C.c_int),
+        "ovs_pastry_find_node_batch": ([vp, vp, vp, u64, i32, i32, vp, u32, vp, vp, vp], C.c_int),
+        "ovs_pastry_route_batch": ([vp, vp, vp, u64, vp, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -808,6 +853,90 @@ class KbrEngine:
                                                  C.c_void_p(out_ptr), None, C.c_void_p(rpcs_ptr) if rpcs_ptr else None,
                                                  DEVICE_PTRS, C.c_void_p(stream) if stream else None),
                   "ovs_broose_route_batch")
+
+    # -- Pastry
+    def pastry_load(self, ids, xy, pp: "PastryParams | None" = None):
+        """The converged Pastry tables (ovs_pastry_load), built on the device by the rule of DESIGN.md §4.
+        params.overlay must be OVERLAY_PASTRY."""
+        ids = keys_array(ids)
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        self._pp = pp if pp is not None else PastryParams.default(routeMsgAcks=0)
+        self._chk(self._L.ovs_pastry_load(self._h, C.byref(self._pp), _ptr(ids), len(ids), _ptr(xy), 0), "ovs_pastry_load")
+        self.n, self.overlay = len(ids), OVERLAY_PASTRY
+
+    def pastry_load_device(self, ids_ptr: int, xy_ptr: int, n: int, pp: "PastryParams | None" = None):
+        self._pp = pp if pp is not None else PastryParams.default(routeMsgAcks=0)
+        self._chk(self._L.ovs_pastry_load(self._h, C.byref(self._pp), C.c_void_p(ids_ptr), n, C.c_void_p(xy_ptr),
+                                          DEVICE_PTRS), "ovs_pastry_load")
+        self.n, self.overlay = n, OVERLAY_PASTRY
+
+    def pastry_load_tables(self, ids, xy, leaf, table, pp: "PastryParams | None" = None):
+        """Explicit Pastry tables as node indices, NONE = unspecified (ovs_pastry_load_tables): leaf (n, L) in
+        the reference's slot order, table (n, rows, 2^bitsPerDigit)."""
+        ids = keys_array(ids)
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        leaf = np.ascontiguousarray(leaf, dtype=np.uint32)
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        pp = pp if pp is not None else PastryParams.default(routeMsgAcks=0)
+        n = len(ids)
+        if leaf.shape != (n, pp.numberOfLeaves):
+            raise ValueError("leaf must be (n, numberOfLeaves)")
+        if table.ndim != 3 or table.shape[0] != n or table.shape[2] != 1 << pp.bitsPerDigit:
+            raise ValueError("table must be (n, rows, 2^bitsPerDigit)")
+        self._chk(self._L.ovs_pastry_load_tables(self._h, C.byref(pp), _ptr(ids), n, _ptr(xy), _ptr(leaf), _ptr(table),
+                                                 table.shape[1], 0), "ovs_pastry_load_tables")
+        self._pp = pp
+        self.n, self.overlay = n, OVERLAY_PASTRY
+
+    def pastry_export(self):
+        """(leaf (n, L), table (n, rows, 2^bitsPerDigit)) of the loaded Pastry tables, NONE = unspecified."""
+        rows = int(self._L.ovs_pastry_num_rows(self._h))
+        if rows < 0:
+            raise KbrError("ovs_pastry_export: ESTATE: no Pastry network loaded")
+        leaf = np.empty((self.n, self._pp.numberOfLeaves), dtype=np.uint32)
+        table = np.empty((self.n, rows, 1 << self._pp.bitsPerDigit), dtype=np.uint32)
+        self._chk(self._L.ovs_pastry_export(self._h, _ptr(leaf), _ptr(table)), "ovs_pastry_export")
+        return leaf, table
+
+    def pastry_find_node(self, node, keys, numRedundantNodes: int = 1, numSiblings: int = 1, max_out: int | None = None):
+        """BasePastry::findNode at node[i] for keys[i] (ovs_pastry_find_node_batch).  Returns (nodes (n, max_out)
+        NONE padded, count, sibling flag, status: bit 0 isSiblingFor's err, bit 1 the reference throws)."""
+        node = np.ascontiguousarray(node, dtype=np.uint32)
+        keys = keys_array(keys)
+        n = len(node)
+        mo = max_out or max(numRedundantNodes + 1, numSiblings, 1)
+        out = np.empty((n, mo), dtype=np.uint32)
+        cnt = np.empty(n, dtype=np.uint8)
+        sib = np.empty(n, dtype=np.uint8)
+        st = np.empty(n, dtype=np.uint8)
+        self._chk(self._L.ovs_pastry_find_node_batch(self._h, _ptr(node), _ptr(keys), n, numRedundantNodes, numSiblings,
+                                                     _ptr(out), mo, _ptr(cnt), _ptr(sib), _ptr(st)),
+                  "ovs_pastry_find_node_batch")
+        return out, cnt, sib, st
+
+    def pastry_lookup(self, keys, src, record_hops: bool = False) -> dict:
+        """Batched semi-recursive one-way routes on a Pastry context (ovs_pastry_route_batch).  Returns numpy
+        arrays by field, as lookup()."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
+        H = max(self.get_params().hopCountMax, 1)
+        hop = np.empty((n, H), dtype=np.uint32) if record_hops else None
+        self._chk(self._L.ovs_pastry_route_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), _ptr(hop), 0, None),
+                  "ovs_pastry_route_batch")
+        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
+        if hop is not None:
+            res["hop_seq"] = hop
+        return res
+
+    def pastry_lookup_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
+        """Device-resident batch (async on `stream`)."""
+        self._chk(self._L.ovs_pastry_route_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n, C.c_void_p(out_ptr),
+                                                 None, DEVICE_PTRS, C.c_void_p(stream) if stream else None),
+                  "ovs_pastry_route_batch")
 
     def epichord_load(self, ids, xy, succ, nsucc, pred, npred, lists_full, cache_off, cache_node, cache_last_ns,
                       cache_ttl_ns):
