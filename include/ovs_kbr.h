@@ -881,8 +881,21 @@ ovs_status  ovs_chord_broadcast_batch(ovs_ctx* ctx, const uint32_t* initiators, 
  * itself).  A join whose route fails leaves its sender without a parent: an iterative lookup past
  * hopCountMax; hopCountMax = 0 (dropped at the source); semi-recursive with hopCountMax = 1 when the first
  * hop is not responsible (sendToKey's hop check precedes forward(), BaseOverlay.cc:1464, 1546).
- * ovs_scribe_multicast_batch is OVS_ESTATE when routingType or hopCountMax differ from the build's. */
+ * ovs_scribe_multicast_batch is OVS_ESTATE when routingType or hopCountMax differ from the build's.
+ *
+ * Scribe on Pastry (additive to ABI 12; test OVS_HAS_SCRIBE_PASTRY): the same five calls on a context loaded
+ * with ovs_pastry_load -- the reference's own [Config Scribe] (overlayType = PastryModules,
+ * useCommonAPIforward = true), under the Pastry route's conditions (semi-recursive, no per-hop acks,
+ * numSiblings 1, recNumRedundantNodes 1..8).  The parent of (group, x) is the node sendToKey's source step
+ * picks at x for the group key: findNode(K, recNumRedundantNodes, 1) and the candidate loop of
+ * BaseOverlay.cc:1507-1521 with no last hop and source = x; x itself where it is the sibling for K (the
+ * root); none where that step ends in OVS_LOOKUP_NO_NEXT or OVS_LOOKUP_BROKEN.  The hop limit acts as on
+ * Chord.  The publish is a semi-recursive Pastry route with the ScribePublishCall in the KBRTestApp message's
+ * place; records, lengths and the dissemination are the same.  OVS_ENOTSUP, forest and context untouched:
+ * tables from ovs_pastry_load_tables (parent chains there can close into cycles without a root) and whatever
+ * ovs_pastry_route_batch refuses. */
 #define OVS_HAS_SCRIBE 1
+#define OVS_HAS_SCRIBE_PASTRY 1
 #define OVS_SCRIBE_SUBSCRIBER 1u   /* the node itself subscribed */
 #define OVS_SCRIBE_ROOT       2u   /* parent == the node: it answers publishes */
 #define OVS_SCRIBE_FORWARDER  4u   /* it has children */
@@ -914,8 +927,8 @@ typedef struct ovs_scribe_delivery { /* 24 B, one per (message, subscriber reach
 /* group_keys[n_groups], member_group[n_members], member_node[n_members] follow `flags`; duplicate
  * pairs count once.  capacity = the most tree nodes (members and forwarders of all groups) the forest
  * may hold; one more is OVS_ENOMEM.  Any failure leaves the forest of an earlier call in place.
- * OVS_ENOTSUP: explicit tables, arcs of a sharded ring, other overlays, full-recursive, exhaustive and
- * source-routing routing. */
+ * OVS_ENOTSUP: explicit tables, arcs of a sharded ring, overlays other than Chord and Pastry, full-recursive,
+ * exhaustive and source-routing routing; on Pastry everything but semi-recursive routing. */
 ovs_status  ovs_scribe_build(ovs_ctx* ctx, const ovs_key160* group_keys, uint64_t n_groups, const uint32_t* member_group,
                              const uint32_t* member_node, uint64_t n_members, uint64_t capacity, uint32_t flags,
                              void* stream);
@@ -1289,8 +1302,9 @@ ovs_status  ovs_broose_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const u
  * holds the tables fixed.  Implemented: BasePastry::findNode with both optimizeLookup and useRegularNextHop
  * forms, and semi-recursive one-way routes (routingType 1, numSiblings 1, recNumRedundantNodes 1..8) without
  * per-hop acks.  Refused with OVS_ENOTSUP: routeMsgAcks, numberOfNeighbors != 0, bitsPerDigit outside 1..4,
- * odd numberOfLeaves or above 32, the other routing types.  Everything else on a Pastry context --
- * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, every application tier -- is refused with
+ * odd numberOfLeaves or above 32, the other routing types.  Of the application tiers Scribe runs on a
+ * Pastry context built by ovs_pastry_load (ovs_scribe_*, OVS_HAS_SCRIBE_PASTRY).  Everything else on one --
+ * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, every other application tier -- is refused with
  * OVS_ENOTSUP. */
 #define OVS_HAS_PASTRY 1
 enum { OVS_OVERLAY_PASTRY = 6 };

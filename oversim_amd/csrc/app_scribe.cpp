@@ -1,6 +1,7 @@
-// app_scribe.cpp -- Scribe (scribe.hip) on converged Chord rings: the forest of group trees and the
-// multicasts down them.  Joins under iterative routing and every publish are one-way routes
-// (route_device); scribe_check holds the route's refusals for such a ring, so they come first.
+// app_scribe.cpp -- Scribe (scribe.hip) on converged Chord rings and converged Pastry tables: the forest of
+// group trees and the multicasts down them.  Joins under iterative routing and every publish are one-way
+// routes (route_device; pastry_route_device on Pastry); scribe_check holds the route's refusals for such a
+// network, so they come first.  The two overlays differ in the level kernel and the publish route only.
 #include <algorithm>
 #include <cstring>
 
@@ -18,7 +19,17 @@ ovs_status scribe_check(ovs_ctx* c)
     if (c->overlay == OVS_OVERLAY_KADEMLIA) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings, not Kademlia");
     if (c->overlay == OVS_OVERLAY_KOORDE) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings, not Koorde");
     if (c->overlay == OVS_OVERLAY_EPICHORD) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings, not EpiChord");
-    if (c->overlay != OVS_OVERLAY_CHORD) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings");
+    if (c->overlay == OVS_OVERLAY_PASTRY) {
+        // the reference's own Scribe configuration; the route's refusals are ovs_pastry_route_batch's, in its order
+        if (!c->pastry_rule)
+            return fail(c, OVS_ENOTSUP, "Scribe on explicit tables (ovs_pastry_load_tables): parent chains there can close "
+                                        "into cycles that hold no root (converged tables, ovs_pastry_load, only)");
+        ovs_status st = check_common(c, c->P);
+        if (st != OVS_OK) return st;
+        if (const char* why = pastry_route_refusal(c->P, c->pastry_bp)) return fail(c, OVS_ENOTSUP, why);
+        return OVS_OK;
+    }
+    if (c->overlay != OVS_OVERLAY_CHORD) return fail(c, OVS_ENOTSUP, "Scribe is implemented for Chord rings and Pastry");
     if (!c->ideal)
         return fail(c, OVS_ENOTSUP, "Scribe on explicit tables: the next hop there depends on more than (node, key), so the "
                                     "tree depends on the order of the joins (converged rings only)");
@@ -132,13 +143,18 @@ ovs_status ovs_scribe_build(ovs_ctx* c, const ovs_key160* group_keys, uint64_t G
     // the hop limit acts on routed join messages only: under iterative routing the levels left are the
     // responsible nodes' joins through themselves, which a local lookup delivers without a hop check
     const int join_hcm = c->P.routingType == 0 ? 2 : c->P.hopCountMax;
+    const bool pastry = c->overlay == OVS_OVERLAY_PASTRY;
     for (uint64_t level = 0; hi > lo && level <= c->n; ++level) {
-        HIPCHK(c, launch_scribe_level(V, dgk, q, par, lo, hi, capacity, tab, hsize - 1, ctl, join_hcm, s));
+        if (pastry)
+            HIPCHK(c, launch_scribe_level_pastry(c->pastry, dgk, q, par, lo, hi, capacity, tab, hsize - 1, ctl, join_hcm,
+                                                 c->P.recNumRedundantNodes, s));
+        else
+            HIPCHK(c, launch_scribe_level(V, dgk, q, par, lo, hi, capacity, tab, hsize - 1, ctl, join_hcm, s));
         HIPCHK(c, read_ctl(h, ctl, 2, s));
         if ((st = ctl_status()) != OVS_OK) return st;
         lo = hi; hi = h[0];
     }
-    if (hi > lo) return fail(c, OVS_EDEVICE, "Scribe build: the joins did not end (ring not converged?)");
+    if (hi > lo) return fail(c, OVS_EDEVICE, "Scribe build: the joins did not end (network not converged?)");
     const uint64_t T = hi;
 
     ScribeForest NF;
@@ -278,7 +294,8 @@ ovs_status ovs_scribe_multicast_batch(ovs_ctx* c, const uint32_t* msg_group, con
     // the publish is routed under this call's message length: a copy of the parameters, the context's stay
     ovs_params PR = c->P;
     PR.testMsgSize = call_bytes;
-    st = route_device(c, PR, F, keys, ds, nm, route, nullptr, nullptr, s);
+    st = c->overlay == OVS_OVERLAY_PASTRY ? pastry_route_device(c, PR, F, keys, ds, nm, route, nullptr, s)
+                                          : route_device(c, PR, F, keys, ds, nm, route, nullptr, nullptr, s);
     if (st != OVS_OK) return st;
     HIPCHK(c, launch_scribe_publish(SF, SC, c->xy, route, dg, ds, df, nm, dout, queue, s));
     h[0] = nm;

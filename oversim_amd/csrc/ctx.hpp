@@ -71,6 +71,7 @@ struct ovs_ctx {
     // pastry leaf sets and routing tables (ovs_pastry_load / _load_tables; on the sorted ids in recs / xy)
     ovs::PastryTables pastry{};
     ovs_pastry_params pastry_bp{};
+    bool pastry_rule = false;            // the tables came from the rule (ovs_pastry_load), not from ovs_pastry_load_tables
     ovs::CachedBuf kvis;                 // internal visited lists (K3 without hop_seq, K2x without responders)
     // K1's key-order buffers (ksort.hip): sorted keys, sources, caller indices and the sort's
     // histograms, one allocation shared by the calls on this context like kvis
@@ -177,6 +178,10 @@ ovs_status route_check(ovs_ctx* c, const ovs_params& P, hipStream_t s);
 // F is the call's frame (exhaustive-iterative Kademlia takes a temporary from it).
 ovs_status route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
                         ovs_route_out* dout, uint32_t* dhop, uint32_t* drpc, hipStream_t s);
+// route_device's counterpart on a Pastry context (ovs_pastry.cpp): n > 0 semi-recursive routes on device
+// pointers, queued on s, after check_common, pastry_route_refusal and check_sources
+ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
+                               ovs_route_out* dout, uint32_t* dhop, hipStream_t s);
 // The same for LookupCalls.  lookup_check resolves num_siblings (< 0: the overlay's maximum) into *ns;
 // dsib has max(ns, 1) entries per lookup.
 ovs_status lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_siblings, hipStream_t s, int32_t* ns);

@@ -1,6 +1,7 @@
 // ovs_pastry.cpp -- the Pastry entry points of the C ABI (include/ovs_kbr.h): the loaders, the export, the
-// findNode batch and the semi-recursive route.  The generic calls and the application tiers refuse a Pastry
-// context through refuse_dedicated (ovs_route.cpp).
+// findNode batch and the semi-recursive route (pastry_route_device: the public call's and Scribe's publish leg).
+// The generic calls and the other application tiers refuse a Pastry context through refuse_dedicated
+// (ovs_route.cpp); Scribe runs on one (app_scribe.cpp).
 #include <string>
 #include <vector>
 
@@ -19,6 +20,21 @@ ovs_status load_begin(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_key160*
 }
 
 }  // namespace
+
+namespace ovs {
+
+ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, CallFrame&, const K160* dk, const uint32_t* ds, uint64_t n,
+                               ovs_route_out* dout, uint32_t* dhop, hipStream_t s)
+{
+    const uint64_t H = (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
+    if (dhop) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+    const hipError_t e = pastry_route(c->pastry, delay_consts(P), P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout, dhop,
+                                      c->num_cu, s, dyn.get());
+    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry route kernel");
+}
+
+}  // namespace ovs
 
 extern "C" {
 
@@ -66,6 +82,7 @@ ovs_status ovs_pastry_load(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_ke
         if (F.finish() != hipSuccess) return frame_fail(c, F);
     }
     c->pastry_bp = *bp;
+    c->pastry_rule = true;
     return L.commit();
 }
 
@@ -94,6 +111,7 @@ ovs_status ovs_pastry_load_tables(ovs_ctx* c, const ovs_pastry_params* bp, const
     if (e != hipSuccess) return hip_fail(c, e, "pastry table upload");
     if (F.finish() != hipSuccess) return frame_fail(c, F);
     c->pastry_bp = *bp;
+    c->pastry_rule = false;
     return L.commit();
 }
 
@@ -162,11 +180,7 @@ ovs_status ovs_pastry_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint
     ovs_route_out* dout = F.out(out, n);
     uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
     if (!F.ok()) return frame_fail(c, F);
-    if (dhop) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
-    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-    const hipError_t e = pastry_route(c->pastry, delay_consts(P), P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout, dhop,
-                                      c->num_cu, s, dyn.get());
-    if (e != hipSuccess) return hip_fail(c, e, "pastry route kernel");
+    if ((st = pastry_route_device(c, P, F, dk, ds, n, dout, dhop, s)) != OVS_OK) return st;
     return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
 }
 

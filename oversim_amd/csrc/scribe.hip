@@ -1,4 +1,5 @@
-// scribe.hip -- Scribe group trees and publishes on a converged Chord ring, for gfx950 (MI355X).
+// scribe.hip -- Scribe group trees and publishes on a converged Chord ring or converged Pastry tables, for
+// gfx950 (MI355X).
 //
 // Forest build (Scribe.cc:113-127, 329-373, 410-431, 459-479; BaseApp.cc:334-395).  On a converged ring
 // the next hop from a node towards a key depends on (node, key) alone, and every node that absorbs a
@@ -15,6 +16,9 @@
 // check) and forward() absorbs it there; any other first hop passes it to sendToKey, whose hop check
 // (1464) comes before callForward (1546-1551): with hopCountMax = 1 the join is discarded unseen, its
 // sender keeps no parent and the first hop joins nothing.  hopCountMax = 0 discards at the source.
+// On converged Pastry tables (the reference's own Scribe configuration) the frontier, the set and the hop
+// limit are the same and the parent is the pick of the Pastry route's source step (k_scribe_level_pastry,
+// pastry_dev.hpp).
 //
 // Then the tree nodes are sorted by (group, node) and the edges by (parent, child) tree-node index,
 // which is (group, parent, child) order: the CSR child lists are in std::set<NodeHandle> order
@@ -28,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "pastry_dev.hpp"
 #include "scribe.hpp"
 #include "tier_dev.hpp"
 
@@ -143,6 +148,36 @@ __global__ __launch_bounds__(256) void k_scribe_level(ChordView V, const K160* _
         const K160 K = gkeys[g];
         uint32_t p = hcm <= 0 ? NONE : next_hop(V, x, K);
         if (hcm == 1 && p != x && p != NONE && !responsible(V, p, K)) p = NONE;
+        par[i] = p;
+        if (p != x && p != NONE) {
+            key = ((uint64_t)g << 32) | p;
+            won = claim(tab, hmask, key, ctl);
+        }
+    }
+    append(won, key, q, cap, ctl);
+}
+
+// The same level on converged Pastry tables: the parent is the pick of sendToKey's source step at x (findNode and
+// the candidate loop with no last hop and source = x: pastry_source_step, the route kernel's own), x itself where
+// it is the sibling for K; a source step that ends in a status drops the join.  A first hop's own sendToKey never
+// refuses a join on rule-built tables (tests/test_scribe_pastry_model.py asserts it), so only its hop check
+// (hopCountMax = 1, unless receipt delivers: the pick is a sibling) is evaluated here.
+__global__ __launch_bounds__(256) void k_scribe_level_pastry(PView V, const K160* __restrict__ gkeys,
+                                                             uint64_t* __restrict__ q, uint32_t* __restrict__ par,
+                                                             uint64_t lo, uint64_t hi, uint64_t cap,
+                                                             unsigned long long* __restrict__ tab, uint64_t hmask,
+                                                             unsigned long long* ctl, int hcm, int nred)
+{
+    const uint64_t i = lo + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    bool won = false;
+    uint64_t key = 0;
+    if (i < hi) {
+        const uint64_t it = q[i];
+        const uint32_t g = (uint32_t)(it >> 32), x = (uint32_t)it;
+        const K160 K = gkeys[g];
+        const PStep st = pastry_source_step(V, x, K, hcm, nred);      // hopCountMax <= 0: OVS_LOOKUP_HOPMAX
+        uint32_t p = st.status == PSTEP_FORWARD ? st.next : st.status == OVS_LOOKUP_OK ? x : NONE;
+        if (hcm == 1 && p != x && p != NONE && !pastry_is_sibling(V, p, K)) p = NONE;
         par[i] = p;
         if (p != x && p != NONE) {
             key = ((uint64_t)g << 32) | p;
@@ -466,6 +501,17 @@ hipError_t launch_scribe_level(const ChordView& V, const K160* gkeys, uint64_t* 
     if (!grid_ok(blocks256(hi - lo))) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scribe_level, dim3((unsigned)blocks256(hi - lo)), dim3(256), 0, s, V, gkeys, q, par, lo, hi, cap, tab, hmask,
                        ctl, hopCountMax);
+    return hipGetLastError();
+}
+
+hipError_t launch_scribe_level_pastry(const PastryTables& t, const K160* gkeys, uint64_t* q, uint32_t* par, uint64_t lo,
+                                      uint64_t hi, uint64_t cap, unsigned long long* tab, uint64_t hmask,
+                                      unsigned long long* ctl, int hopCountMax, int recNumRedundantNodes, hipStream_t s)
+{
+    if (hi <= lo) return hipSuccess;
+    if (!grid_ok(blocks256(hi - lo))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scribe_level_pastry, dim3((unsigned)blocks256(hi - lo)), dim3(256), 0, s, make_view(t), gkeys, q, par, lo, hi,
+                       cap, tab, hmask, ctl, hopCountMax, recNumRedundantNodes);
     return hipGetLastError();
 }
 

@@ -1,6 +1,8 @@
-// scribe.hpp -- Scribe group trees and publishes on a converged Chord ring (scribe.hip; internal).
+// scribe.hpp -- Scribe group trees and publishes on a converged Chord ring or converged Pastry tables
+// (scribe.hip; internal).
 #pragma once
 #include "engine.hpp"
+#include "pastry.hpp"
 
 namespace ovs {
 
@@ -50,6 +52,11 @@ hipError_t launch_scribe_init(const uint32_t* mgroup, const uint32_t* mnode, uin
 hipError_t launch_scribe_level(const ChordView& V, const K160* gkeys, uint64_t* q, uint32_t* par, uint64_t lo,
                                uint64_t hi, uint64_t cap, unsigned long long* tab, uint64_t hmask,
                                unsigned long long* ctl, int hopCountMax, hipStream_t s);
+// the same level on converged Pastry tables: the parent is the pick of the route's source step at the node
+// (pastry_source_step), the node itself where it is the sibling for the key
+hipError_t launch_scribe_level_pastry(const PastryTables& t, const K160* gkeys, uint64_t* q, uint32_t* par, uint64_t lo,
+                                      uint64_t hi, uint64_t cap, unsigned long long* tab, uint64_t hmask,
+                                      unsigned long long* ctl, int hopCountMax, int recNumRedundantNodes, hipStream_t s);
 // iterative routing: the joins of q[0 .. m0) as a route batch's inputs, and its results as their parents
 hipError_t launch_scribe_route_in(const K160* gkeys, const uint64_t* q, uint64_t m0, K160* keys, uint32_t* src,
                                   hipStream_t s);

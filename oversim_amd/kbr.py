@@ -1232,8 +1232,9 @@ class KbrEngine:
 
     # -- Scribe
     def scribe_build(self, group_keys, member_group, member_node, capacity: int | None = None):
-        """Build the Scribe forest of all groups (ovs_scribe_build): member_node[i] subscribes to group
-        member_group[i] (an index into group_keys).  capacity = the most tree nodes the forest may hold
+        """Build the Scribe forest of all groups (ovs_scribe_build) on a converged Chord ring (chord_load) or
+        converged Pastry tables (pastry_load): member_node[i] subscribes to group member_group[i] (an index
+        into group_keys).  capacity = the most tree nodes the forest may hold
         (default: memberships * 64 + groups, far above a Chord path's length).  Returns (tree nodes,
         edges, groups with a root)."""
         gk = keys_array(group_keys) if len(group_keys) else np.zeros((0, 5), np.uint32)
