@@ -1300,9 +1300,10 @@ ovs_status  ovs_broose_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const u
  * smaller keys in slots 0 .. L/2 - 1 with the predecessor last, the bigger keys from slot L/2 with the
  * successor first) and a routing table of rows x 2^bitsPerDigit slots (PastryRoutingTable.cc).  A batch
  * holds the tables fixed.  Implemented: BasePastry::findNode with both optimizeLookup and useRegularNextHop
- * forms, and semi-recursive one-way routes (routingType 1, numSiblings 1, recNumRedundantNodes 1..8) without
- * per-hop acks.  Refused with OVS_ENOTSUP: routeMsgAcks, numberOfNeighbors != 0, bitsPerDigit outside 1..4,
- * odd numberOfLeaves or above 32, the other routing types.  Of the application tiers Scribe runs on a
+ * forms, semi-recursive one-way routes (routingType 1, numSiblings 1, recNumRedundantNodes 1..8) without
+ * per-hop acks, and iterative lookups (routingType 0: ovs_pastry_lookup_batch, ovs_pastry_iterative_route_batch
+ * below).  Refused with OVS_ENOTSUP: routeMsgAcks, numberOfNeighbors != 0, bitsPerDigit outside 1..4,
+ * odd numberOfLeaves or above 32, the full-recursive and source-routing types.  Of the application tiers Scribe runs on a
  * Pastry context built by ovs_pastry_load (ovs_scribe_*, OVS_HAS_SCRIBE_PASTRY).  Everything else on one --
  * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, every other application tier -- is refused with
  * OVS_ENOTSUP. */
@@ -1355,6 +1356,38 @@ ovs_status  ovs_pastry_find_node_batch(ovs_ctx* ctx, const uint32_t* node, const
  * hop_seq / flags / stream as for ovs_route_batch. */
 ovs_status  ovs_pastry_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
                                    ovs_route_out* out, uint32_t* hop_seq, uint32_t flags, void* stream);
+
+/* ---- Iterative lookups on Pastry (additive to ABI 12; test OVS_HAS_PASTRY_ITERATIVE) ----
+ * IterativeLookup (IterativeLookup.cc:133-244, 803-1170) over BasePastry::findNode on a Pastry context from
+ * either loader, params.routingType = 0: the source's own findNode(key, numberOfLeaves, numSiblings), then
+ * FindNodeCalls from the source, each with the PastryFindNodeExtData object (PastryMessage.msg:35), until a
+ * response carries the siblings flag.  lookupRedundantNodes = lookupParallelPaths = lookupParallelRpcs = 1,
+ * lookupMerge and lookupFinishOnFirstUnchanged off, lookupVisitOnlyOnce on, hopCountMax >= 1 (the hop list is
+ * the visited list); anything else is OVS_ENOTSUP naming the key, another overlay's context OVS_ESTATE.  The
+ * start vector is the source's answer in its own order (nextHops[0] first where useRegularNextHop holds);
+ * its later entries are tried when a FindNodeCall times out (rpcUdpTimeout) or a response names no node.
+ * Status: OVS_LOOKUP_OK, _TIMEOUT, _RPC_TIMEOUT (no next hop left after a timeout), _HOPMAX, _NO_NEXT (the
+ * next hop is visited or dead, or there is none), _BROKEN (findNode throws in the reference).
+ *
+ * ovs_pastry_lookup_batch: LookupCalls at src[i] (BaseOverlay::lookupRpc, BaseOverlay.cc:1938-1968).
+ * num_siblings 1..numberOfLeaves/2, or -1 = getMaxNumSiblings() = numberOfLeaves/2; 0 (an exact-key lookup)
+ * is OVS_ENOTSUP, more OVS_EINVAL.  out as ovs_lookup_batch's; siblings = n * num_siblings node indices (the
+ * count -1 stands for), the last response's createSiblingVector(key, numSiblings) in order, 0xFFFFFFFF
+ * padded.  hop_seq (n * hopCountMax, the responders in order, 0xFFFFFFFF padded) and rpcs (n FindNodeCall
+ * counts) may be NULL.  No route message is sent, so routeMsgAcks does not matter: either value runs.
+ *
+ * ovs_pastry_iterative_route_batch: the KBRTestApp one-way message under iterative routing: the lookup with
+ * numSiblings = 1 and the route message to getResult()[0] (BaseOverlay.cc:1240-1258); out as
+ * ovs_route_batch's.  That last message passes routeMsgAcks, so routeMsgAcks = true is OVS_ENOTSUP as at
+ * ovs_pastry_route_batch.
+ *
+ * keys / src / flags / stream as for ovs_route_batch (host calls check the sources). */
+#define OVS_HAS_PASTRY_ITERATIVE 1
+ovs_status  ovs_pastry_lookup_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                                    int32_t num_siblings, ovs_lookup_out* out, uint32_t* siblings, uint32_t* hop_seq,
+                                    uint32_t* rpcs, uint32_t flags, void* stream);
+ovs_status  ovs_pastry_iterative_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                                             ovs_route_out* out, uint32_t* hop_seq, uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

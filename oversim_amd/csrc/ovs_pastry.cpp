@@ -1,5 +1,6 @@
 // ovs_pastry.cpp -- the Pastry entry points of the C ABI (include/ovs_kbr.h): the loaders, the export, the
-// findNode batch and the semi-recursive route (pastry_route_device: the public call's and Scribe's publish leg).
+// findNode batch, the semi-recursive route (pastry_route_device: the public call's and Scribe's publish leg) and
+// the iterative lookup (pastry_iter_call: the LookupCall batch and the one-way route under iterative routing).
 // The generic calls and the other application tiers refuse a Pastry context through refuse_dedicated
 // (ovs_route.cpp); Scribe runs on one (app_scribe.cpp).
 #include <string>
@@ -17,6 +18,75 @@ ovs_status load_begin(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_key160*
     if (const char* why = pastry_shape_refusal(*bp)) return fail(c, OVS_ENOTSUP, why);
     if (n < 2) return fail(c, OVS_EINVAL, "Pastry needs at least 2 nodes");
     return upload_nodes(c, ids, n, xy, dev);
+}
+
+// Every FindNodeCall and FindNodeResponse of a Pastry lookup carries the PastryFindNodeExtData object:
+// BasePastry::createLookup (BasePastry.cc:1212-1239) hands one to the lookup, createFindNodeCall copies it into
+// each call (IterativeLookup.cc:385-388) -- the first from the lookup's own, the later ones from the response
+// before (907-920) -- and findNodeRpc moves it from the call to the response (BaseOverlay.cc:1903-1907).
+// PASTRYFINDNODEEXTDATA_L = NODEHANDLE_L + HOPCOUNT_L = 224 bits (PastryMessage.msg:35), 28 B.
+DelayConsts pastry_iter_delay_consts(const ovs_params& P)
+{
+    DelayConsts d = delay_consts(P);     // measureAuthBlock is in respBase
+    auto bw = [&](int32_t bytes) { return simtime_host((double)((int64_t)bytes * 8) / P.datarate, P.simtimeRound); };
+    d.callBytes += 28;
+    d.respBase += 28;
+    d.msgCall = 2 * bw(d.callBytes) + d.access2;
+    d.msgResp1 = 2 * bw(d.respBase + d.respPerNode) + d.access2;
+    d.msgRespSib = d.msgResp1;
+    d.bwCall = bw(d.callBytes);
+    for (int i = 0; i <= 16; ++i) d.bwResp[i] = bw(d.respBase + d.respPerNode * i);
+    return d;
+}
+
+// the two iterative entry points: lout + siblings (a LookupCall) or rout (the one-way route)
+ovs_status pastry_iter_call(ovs_ctx* c, const char* name, bool route, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                            int32_t ns, ovs_route_out* rout, ovs_lookup_out* lout, uint32_t* siblings, uint32_t* hop_seq, uint32_t* rpcs,
+                            uint32_t flags, void* stream)
+{
+    if (!c || (n && (!keys || !src || (route ? !rout : !lout || !siblings)))) return OVS_EINVAL;
+    if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
+    const ovs_params& P = c->P;
+    if (const char* why = pastry_iterative_refusal(P, c->pastry_bp, route)) return fail(c, OVS_ENOTSUP, why);
+    ovs_status st = check_common(c, P);
+    if (st != OVS_OK) return st;
+    // getMaxNumSiblings (BasePastry.cc:1090-1093); lookupRpc turns a negative count into it (BaseOverlay.cc:1940-1944)
+    const int maxsib = c->pastry.sh.L / 2;
+    if (ns < 0) ns = maxsib;
+    if (ns == 0)
+        return fail(c, OVS_ENOTSUP, std::string(name) + ": exact-key lookups (num_siblings = 0) are not implemented on Pastry");
+    if (ns > maxsib) return fail(c, OVS_EINVAL, "numSiblings too big! (num_siblings must be 1..numberOfLeaves/2 or -1)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    if (n == 0) return OVS_OK;
+    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
+    const uint64_t H = (uint64_t)P.hopCountMax;
+    CallFrame F(dev, s);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dro = rout ? F.out(rout, n) : nullptr;
+    ovs_lookup_out* dlo = lout ? F.out(lout, n) : nullptr;
+    uint32_t* dsib = siblings ? F.out(siblings, n * (uint64_t)ns) : nullptr;
+    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
+    uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
+    // without a hop_seq request the visited lists live in the context's cached buffer, unpadded: the
+    // kernel reads back only the entries a lookup wrote
+    CachedBuf::Lease vis;
+    if (!dhop) {
+        vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
+        if (!vis) return lease_fail(c, "kvis", vis);
+        dhop = reinterpret_cast<uint32_t*>(vis.data());
+    } else {
+        HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+    }
+    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+    const hipError_t e = pastry_iter(c->pastry, pastry_iter_delay_consts(P), P.hopCountMax, ns, dk, ds, n, dro, dlo, dsib, dhop, drpc,
+                                     c->num_cu, s, dyn.get());
+    vis.release();
+    if (e != hipSuccess) return hip_fail(c, e, "pastry iterative lookup kernel");
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
 }
 
 }  // namespace
@@ -182,6 +252,21 @@ ovs_status ovs_pastry_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint
     if (!F.ok()) return frame_fail(c, F);
     if ((st = pastry_route_device(c, P, F, dk, ds, n, dout, dhop, s)) != OVS_OK) return st;
     return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+}
+
+ovs_status ovs_pastry_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, int32_t num_siblings,
+                                   ovs_lookup_out* out, uint32_t* siblings, uint32_t* hop_seq, uint32_t* rpcs, uint32_t flags,
+                                   void* stream)
+{
+    return pastry_iter_call(c, "ovs_pastry_lookup_batch", false, keys, src, n, num_siblings, nullptr, out, siblings, hop_seq, rpcs, flags,
+                            stream);
+}
+
+ovs_status ovs_pastry_iterative_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_route_out* out,
+                                            uint32_t* hop_seq, uint32_t flags, void* stream)
+{
+    return pastry_iter_call(c, "ovs_pastry_iterative_route_batch", true, keys, src, n, 1, out, nullptr, nullptr, hop_seq,
+                            nullptr, flags, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,9 @@
 // k_pastry_route, which runs one lane per semi-recursive route message (BaseOverlay::sendToKey's recursive branch,
 // pastry_send_to_key) on the persistent-slice scheduler of persist.hpp.  A hop reads the node's record, its leaf
 // row and the one table slot the key addresses; the table rows are scanned only for the closer-node fallback and
-// when the first candidate of a numRedundantNodes > 1 answer is refused.
+// when the first candidate of a numRedundantNodes > 1 answer is refused.  k_pastry_iter runs one lane per
+// IterativeLookup (a LookupCall with its sibling vector, or the one-way message under iterative routing) on the
+// same scheduler: FindNodeCalls from the source, one pastry_find_node_dev per responder.
 #include "pastry_dev.hpp"
 
 #include "broose_host.hpp"
@@ -252,6 +254,221 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
     }
 }
 
+// ---------------------------------------------------------------------------
+// the iterative lookup
+
+// Entry idx of the source's own findNode answer (IterativeLookup.cc:158-160: numRedundantNodes =
+// getMaxNumRedundantNodes() = numberOfLeaves), NONE past its end; *seen: probe is among the entries before it.
+// The path's start vector is that answer in its own order and unbounded (merge off: IterativePathLookup::add
+// push_backs, 1189-1194), so it is walked again here, on the rare paths that look past its first entry,
+// rather than kept.
+__device__ uint32_t source_entry(const PView& V, uint32_t S, const K160& K, int nsib, int idx, uint32_t probe, bool* seen)
+{
+    const PRec Rs = load_prec(V.rec, S);
+    const PAns as = pastry_find_node_dev(V, S, Rs, K, nsib);
+    PIter it = iter_start();
+    *seen = false;
+    uint32_t x = NONE;
+    for (int i = 0; i <= idx; ++i) {
+        x = answer_next(V, S, Rs, K, as, V.sh.L, nsib, it);
+        if (x == NONE) break;
+        if (i < idx && x == probe) *seen = true;
+    }
+    return x;
+}
+
+// One lane per IterativeLookup on Pastry (IterativeLookup.cc with lookupRedundantNodes = lookupParallelPaths =
+// lookupParallelRpcs = 1, merge off, visitOnlyOnce, finishOnFirstUnchanged off): one loop iteration is the
+// source's local findNode (start, 133-244) or one FindNodeCall with its response or timeout.  lout: a LookupCall
+// with nsib siblings (sibs: nq * nsib); rout: the KBRTestApp one-way message under iterative routing (nsib = 1),
+// which adds the route message to getResult()[0] (BaseOverlay.cc:1240-1258).  hopseq (nq * hcm, hcm >= 1) holds
+// the responders in order and is, with the source, the visited set.  Every call and every response carries the
+// PastryFindNodeExtData object (BasePastry.cc:1212-1239, IterativeLookup.cc:385-388, BaseOverlay.cc:1903-1907;
+// its bits are in DC); iterativeJoinHook (Pastry.cc:591-614) only counts joinHopCount in it for a lookup that is
+// no join and changes no answer, so nothing of it is carried.
+__global__ __launch_bounds__(256) void k_pastry_iter(PView V, DelayConsts DC, int hcm, int nsib, const K160* __restrict__ qkeys,
+                                                     const uint32_t* __restrict__ qsrc, uint64_t nq, uint64_t chunk, PDyn dy,
+                                                     ovs_route_out* __restrict__ rout, ovs_lookup_out* __restrict__ lout,
+                                                     uint32_t* __restrict__ sibs, uint32_t* __restrict__ hopseq,
+                                                     uint32_t* __restrict__ rpcs)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    uint64_t cursor = wave * chunk;
+    uint64_t end = min(cursor + chunk, dy.ctr ? dy.from : nq);
+    bool more = dy.ctr != nullptr;
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t H = (uint64_t)hcm;
+
+    bool active = false, local = true, srcvec = false;
+    uint64_t q = 0;
+    K160 K;
+    K.w[0] = K.w[1] = K.w[2] = K.w[3] = K.w[4] = 0;
+    uint32_t S = 0, cur = 0, nrpc = 0;
+    double sx = 0, sy = 0;            // the source
+    int64_t t = 0;
+    int hops = 0, ntry = 0, ndead = 0;
+    while (true) {
+        const uint64_t need = __ballot(!active);
+        if (more && need != 0 && cursor >= end) {
+            const uint64_t nb = persist_claim_chunk<KP_TUNE.dyn_chunk>(dy.ctr, dy.from, lane);
+            if (nb < nq) {
+                cursor = nb;
+                end = min(nb + (uint64_t)KP_TUNE.dyn_chunk, nq);
+            } else {
+                more = false;
+            }
+        }
+        if (need != 0 && cursor < end) {
+            const uint64_t mine = cursor + (uint64_t)__popcll(need & lt_mask);
+            if (!active && mine < end) {
+                q = mine;
+                active = true;
+                local = true;
+                srcvec = false;
+                K = qkeys[q];
+                S = qsrc[q];
+                cur = S;
+                t = 0; hops = 0; ntry = 0; ndead = 0; nrpc = 0;
+            }
+            cursor += (uint64_t)__popcll(need);
+        }
+        if (!__any(active)) break;
+        if (!active) continue;
+
+        uint32_t* seq = hopseq + q * H;
+        uint32_t* sv = sibs ? sibs + q * (uint64_t)nsib : nullptr;
+        const PRec Rc = load_prec(V.rec, cur);
+        const PAns a = pastry_find_node_dev(V, cur, Rc, K, nsib);
+        uint8_t status = OVS_LOOKUP_OK;
+        bool fin = false;
+        uint32_t Rn = NONE, nx = NONE;
+        int cnt = 0;                  // nodes in this answer
+        bool walk = false;            // the path goes on with the start vector's next unused entry
+        if (!a.broken) {
+            PIter it = iter_start();
+            if (a.sib) {
+                // the sibling vector: the lookup's result where this answer is accepted (addSibling, 436-440)
+                while (true) {
+                    const uint32_t x = answer_next(V, cur, Rc, K, a, 1, nsib, it);
+                    if (x == NONE) break;
+                    if (cnt == 0) Rn = x;
+                    if (sv) sv[cnt] = x;
+                    ++cnt;
+                }
+            } else {
+                nx = answer_next(V, cur, Rc, K, a, local ? V.sh.L : 1, nsib, it);
+                cnt = nx != NONE ? 1 : 0;
+            }
+        }
+        if (local) {
+            // IterativeLookup::start (133-244); the source counts as visited (164)
+            local = false;
+            sx = Rc.x; sy = Rc.y;
+            if (a.broken) { fin = true; status = OVS_LOOKUP_BROKEN; }
+            else if (a.sib) fin = true;                                                // the key is local (186-195)
+            else if (nx == NONE || nx == S) { fin = true; status = OVS_LOOKUP_NO_NEXT; }  // no next hops (167-170);
+            else { cur = nx; ntry = 1; srcvec = true; }                                // the first entry is visited (1111)
+        } else if (a.broken) {
+            ++nrpc;
+            fin = true; status = OVS_LOOKUP_BROKEN;    // the responder's findNode errors
+        } else {
+            // FindNodeCall S -> cur and its FindNodeResponse with cnt NodeHandles
+            ++nrpc;
+            const int64_t cd = coord_ns(sx, sy, Rc.x, Rc.y, DC.round);
+            const int64_t rtt = DC.msgCall + resp_ns(DC, cnt) + 2 * cd;
+            if (rtt >= DC.rpcTimeout) {
+                // handleTimeout (935-1023): cur is dead; sendRpc goes on with the next unused next hop, and only
+                // the start vector holds more than one: every response that names a node replaces them by it
+                t += DC.rpcTimeout;
+                cnt = 0;
+                if (t > DC.lookupTimeout) { fin = true; status = OVS_LOOKUP_TIMEOUT; }
+                else if (!srcvec) { fin = true; status = OVS_LOOKUP_RPC_TIMEOUT; }
+                else { ++ndead; walk = true; status = OVS_LOOKUP_RPC_TIMEOUT; }
+            } else {
+                t += rtt;
+                if (t > DC.lookupTimeout) { fin = true; status = OVS_LOOKUP_TIMEOUT; cnt = 0; }
+                else {
+                    // handleResponse (803-921); hops < hcm here: sendRpc checks it before every call
+                    seq[hops] = cur;
+                    ++hops;
+                    if (a.sib) fin = true;                                             // 897-905
+                    else if (hops >= hcm) { fin = true; status = OVS_LOOKUP_HOPMAX; }  // sendRpc (1074-1086)
+                    else if (cnt == 0) {
+                        // no node: the next hops stay as they are (839-846) and sendRpc tries the remaining ones
+                        // (1095-1100); a response's single node is used up
+                        if (srcvec) { walk = true; status = OVS_LOOKUP_NO_NEXT; }
+                        else { fin = true; status = OVS_LOOKUP_NO_NEXT; }
+                    } else {
+                        // replace mode (841-843); visitOnlyOnce (1111): not the source, no earlier responder; nor
+                        // a node that timed out (getNextEntry, 1172-1182): a start-vector entry tried and not visited
+                        srcvec = false;
+                        bool seen = nx == S;
+                        for (int i = 0; i < hops && !seen; ++i) seen = seq[i] == nx;
+                        if (seen) { fin = true; status = OVS_LOOKUP_NO_NEXT; }
+                        else cur = nx;
+                    }
+                }
+            }
+        }
+        if (walk || (!fin && ndead > 0 && !srcvec)) {
+            bool dead;
+            const uint32_t x = source_entry(V, S, K, nsib, ntry, walk ? NONE : cur, &dead);
+            if (walk) {
+                ++ntry;
+                bool seen = x == NONE || x == S;
+                for (int i = 0; i < hops && !seen; ++i) seen = seq[i] == x;
+                if (seen) fin = true;                  // status: what the path was doing when it ran out
+                else { cur = x; status = OVS_LOOKUP_OK; }
+            } else if (dead) {
+                fin = true; status = OVS_LOOKUP_NO_NEXT;
+            }
+        }
+        if (fin) {
+            const bool ok = status == OVS_LOOKUP_OK;
+            if (!ok) cnt = 0;
+            if (sv)
+                for (int j = cnt; j < nsib; ++j) sv[j] = NONE;
+            if (rout) {
+                ovs_route_out o;
+                o.hops = (uint16_t)hops;
+                o.status = status;
+                if (ok) {
+                    o.responsible = Rn;
+                    o.one_way_hops = (uint8_t)(hops + (Rn != S ? 1 : 0));
+                    int64_t lat = t;
+                    if (Rn != S) {
+                        // sendRouteMessage to getResult()[0] (BaseOverlay.cc:1253-1257): the closest node the last
+                        // responder knows, not always that responder
+                        double rx = Rc.x, ry = Rc.y;
+                        if (Rn != cur) {
+                            const PRec Rr = load_prec(V.rec, Rn);
+                            rx = Rr.x; ry = Rr.y;
+                        }
+                        lat += DC.msgRoute + coord_ns(sx, sy, rx, ry, DC.round);
+                    }
+                    o.latency_ns = lat;
+                } else {
+                    o.responsible = NONE;
+                    o.one_way_hops = 0;
+                    o.latency_ns = -1;
+                }
+                rout[q] = o;
+            } else {
+                ovs_lookup_out o;
+                o.num_siblings = (uint32_t)cnt;
+                o.hops = (uint16_t)hops;
+                o.status = status;
+                o.is_valid = ok ? 1 : 0;
+                o.latency_ns = ok ? t : -1;
+                lout[q] = o;
+            }
+            if (rpcs) rpcs[q] = nrpc;
+            active = false;
+        }
+    }
+}
+
 inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 hipError_t alloc_tables(uint32_t n, const PastryShape& sh, int rows, PastryTables& t)
@@ -365,6 +582,22 @@ hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCou
     const PDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
     hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, recNumRedundantNodes, keys,
                        src, nq, pl.chunk, dy, out, hopseq);
+    return hipGetLastError();
+}
+
+hipError_t pastry_iter(const PastryTables& t, const DelayConsts& DC, int hopCountMax, int numSiblings, const K160* keys,
+                       const uint32_t* src, uint64_t nq, ovs_route_out* rout, ovs_lookup_out* lout, uint32_t* siblings,
+                       uint32_t* hopseq, uint32_t* rpcs, int num_cu, hipStream_t st, unsigned long long* dyn)
+{
+    if (nq == 0) return hipSuccess;
+    // the hop list holds hopCountMax responders and is the visitOnlyOnce list: no limit, no list
+    if (!hopseq || hopCountMax < 1 || numSiblings < 1 || numSiblings > t.sh.L / 2 || !rout == !lout || (rout && numSiblings != 1))
+        return hipErrorInvalidValue;
+    using K = PersistKernel<k_pastry_iter>;
+    const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
+    const PDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+    hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, numSiblings, keys, src, nq,
+                       pl.chunk, dy, rout, lout, siblings, hopseq, rpcs);
     return hipGetLastError();
 }
 

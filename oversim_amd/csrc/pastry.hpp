@@ -49,5 +49,12 @@ hipError_t pastry_find_node(const PastryTables& t, const uint32_t* node, const K
 hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCountMax, int recNumRedundantNodes, const K160* keys,
                         const uint32_t* src, uint64_t nq, ovs_route_out* out, uint32_t* hopseq, int num_cu, hipStream_t st,
                         unsigned long long* dyn = nullptr);
+// batched iterative lookups (k_pastry_iter): LookupCalls with numSiblings 1..numberOfLeaves/2 into lout and
+// siblings (nq * numSiblings, may be nullptr), or one-way routes (numSiblings 1) into rout -- one of the two.
+// hopseq (nq * hopCountMax, hopCountMax >= 1) is required: it is the visited list; rpcs may be nullptr.  DC
+// carries the call and response lengths with the PastryFindNodeExtData object.
+hipError_t pastry_iter(const PastryTables& t, const DelayConsts& DC, int hopCountMax, int numSiblings, const K160* keys,
+                       const uint32_t* src, uint64_t nq, ovs_route_out* rout, ovs_lookup_out* lout, uint32_t* siblings,
+                       uint32_t* hopseq, uint32_t* rpcs, int num_cu, hipStream_t st, unsigned long long* dyn = nullptr);
 
 }  // namespace ovs

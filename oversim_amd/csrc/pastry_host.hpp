@@ -58,6 +58,28 @@ inline const char* pastry_route_refusal(const ovs_params& P, const ovs_pastry_pa
     return pastry_shape_refusal(bp);
 }
 
+// What ovs_pastry_lookup_batch and ovs_pastry_iterative_route_batch refuse before they look at the batch.  route:
+// the one-way message, whose final sendRouteMessage passes routeMsgAcks (BaseOverlay.cc:1254-1257); the LookupCall
+// sends FindNodeCalls only and runs with either value.
+inline const char* pastry_iterative_refusal(const ovs_params& P, const ovs_pastry_params& bp, bool route)
+{
+    if (P.routingType != 0)
+        return "Pastry: iterative lookups run with routingType = iterative (semi-recursive routes: ovs_pastry_route_batch)";
+    if (P.hopCountMax < 1)
+        return "Pastry: iterative lookups need hopCountMax >= 1 (the hop list is the visitOnlyOnce list)";
+    if (P.lookupRedundantNodes != 1) return "Pastry: iterative lookups implement lookupRedundantNodes = 1";
+    if (P.lookupParallelRpcs != 1) return "Pastry: iterative lookups implement lookupParallelRpcs = 1";
+    if (P.lookupParallelPaths != 1) return "Pastry: iterative lookups implement lookupParallelPaths = 1";
+    if (P.lookupMerge) return "Pastry: iterative lookups implement lookupMerge = false";
+    if (!P.lookupVisitOnlyOnce) return "Pastry: iterative lookups implement lookupVisitOnlyOnce = true";
+    if (P.lookupFinishOnFirstUnchanged) return "Pastry: iterative lookups implement lookupFinishOnFirstUnchanged = false";
+    if (route && bp.routeMsgAcks)
+        return "Pastry: routeMsgAcks = true is not implemented (the per-hop NextHopCall ack shares the forwarder's "
+               "transmit queue with the forwarded message, DESIGN.md §9); set routeMsgAcks = false";
+    if (route && P.numSiblings != 1) return "Pastry routes implement numSiblings = 1";
+    return pastry_shape_refusal(bp);
+}
+
 // KeyRingMetric::distance (Comparator.h:121-131) = PastryStateObject::keyDist (PastryStateObject.cc:107-132)
 OVS_HD K160 p_ring_dist(const K160& x, const K160& y)
 {

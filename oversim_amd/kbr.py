@@ -515,6 +515,8 @@ def lib() -> C.CDLL:
         "ovs_pastry_export": ([vp, vp, vp], C.c_int),
         "ovs_pastry_find_node_batch": ([vp, vp, vp, u64, i32, i32, vp, u32, vp, vp, vp], C.c_int),
         "ovs_pastry_route_batch": ([vp, vp, vp, u64, vp, vp, u32, vp], C.c_int),
+        "ovs_pastry_lookup_batch": ([vp, vp, vp, u64, i32, vp, vp, vp, vp, u32, vp], C.c_int),
+        "ovs_pastry_iterative_route_batch": ([vp, vp, vp, u64, vp, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -937,6 +939,62 @@ class KbrEngine:
         self._chk(self._L.ovs_pastry_route_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n, C.c_void_p(out_ptr),
                                                  None, DEVICE_PTRS, C.c_void_p(stream) if stream else None),
                   "ovs_pastry_route_batch")
+
+    def pastry_lookup_call(self, keys, src, num_siblings: int = 1, record_hops: bool = False) -> dict:
+        """Batched iterative LookupCalls on a Pastry context (ovs_pastry_lookup_batch; params.routingType = 0).
+        num_siblings = -1 is getMaxNumSiblings() = numberOfLeaves / 2.  Returns num_siblings, hops, status,
+        is_valid, latency_ns and rpcs per lookup and `siblings` (n, num_siblings), NONE padded; with record_hops
+        the responders in order as hop_seq (n, hopCountMax)."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        ns = num_siblings if num_siblings >= 0 else self._pp.numberOfLeaves // 2
+        out = np.empty(n, dtype=LOOKUP_OUT_DTYPE)
+        sib = np.empty((n, max(ns, 1)), dtype=np.uint32)
+        hop = np.empty((n, max(self.get_params().hopCountMax, 1)), dtype=np.uint32) if record_hops else None
+        rpcs = np.empty(n, dtype=np.uint32)
+        self._chk(self._L.ovs_pastry_lookup_batch(self._h, _ptr(keys), _ptr(src), n, num_siblings, _ptr(out), _ptr(sib),
+                                                  _ptr(hop), _ptr(rpcs), 0, None), "ovs_pastry_lookup_batch")
+        res = {f: out[f].copy() for f in LOOKUP_OUT_DTYPE.names}
+        res["siblings"] = sib
+        res["rpcs"] = rpcs
+        if hop is not None:
+            res["hop_seq"] = hop
+        return res
+
+    def pastry_lookup_call_device(self, keys_ptr: int, src_ptr: int, n: int, num_siblings: int, out_ptr: int,
+                                  siblings_ptr: int, stream: int | None = None, rpcs_ptr: int | None = None):
+        """Device-resident batch (async on `stream`): out n ovs_lookup_out, siblings n * num_siblings uint32."""
+        self._chk(self._L.ovs_pastry_lookup_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n, num_siblings,
+                                                  C.c_void_p(out_ptr), C.c_void_p(siblings_ptr), None,
+                                                  C.c_void_p(rpcs_ptr) if rpcs_ptr else None, DEVICE_PTRS,
+                                                  C.c_void_p(stream) if stream else None), "ovs_pastry_lookup_batch")
+
+    def pastry_iterative_lookup(self, keys, src, record_hops: bool = False) -> dict:
+        """Batched KBRTestApp one-way routes under iterative routing on a Pastry context
+        (ovs_pastry_iterative_route_batch; params.routingType = 0).  Returns numpy arrays by field, as lookup()."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
+        hop = np.empty((n, max(self.get_params().hopCountMax, 1)), dtype=np.uint32) if record_hops else None
+        self._chk(self._L.ovs_pastry_iterative_route_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), _ptr(hop), 0, None),
+                  "ovs_pastry_iterative_route_batch")
+        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
+        if hop is not None:
+            res["hop_seq"] = hop
+        return res
+
+    def pastry_iterative_lookup_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
+        """Device-resident batch (async on `stream`)."""
+        self._chk(self._L.ovs_pastry_iterative_route_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n,
+                                                           C.c_void_p(out_ptr), None, DEVICE_PTRS,
+                                                           C.c_void_p(stream) if stream else None),
+                  "ovs_pastry_iterative_route_batch")
 
     def epichord_load(self, ids, xy, succ, nsucc, pred, npred, lists_full, cache_off, cache_node, cache_last_ns,
                       cache_ttl_ns):
