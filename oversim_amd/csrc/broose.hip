@@ -28,8 +28,6 @@ void broose_free(BrooseTables& t)
 
 namespace {
 
-__device__ __forceinline__ K160 rkey(const KeyRec* __restrict__ recs, uint64_t i) { return key_of(load_rec(recs + i, 0)); }
-
 __device__ __forceinline__ int kbit(const K160& a, int bit) { return (int)((k_word(a, bit >> 5) >> (bit & 31)) & 1u); }
 
 // ---------------------------------------------------------------------------
@@ -373,26 +371,14 @@ __global__ void k_broose_find_node(BView V, const uint32_t* __restrict__ node, c
 // ---------------------------------------------------------------------------
 // K4: the route
 
-// visitOnlyOnce filter: one bit per node hash; a clear bit proves the node unvisited
-__device__ __forceinline__ uint64_t vis_bit(uint32_t x) { return 1ull << ((x * 0x9E3779B1u) >> 26); }
-
-struct BDyn {
-    unsigned long long* ctr;
-    uint64_t from;
-};
 constexpr PersistTune K4_TUNE{0.70, 64};
 
 __global__ __launch_bounds__(256) void k_broose_route(BView V, DelayConsts DC, int hcm, const K160* __restrict__ qkeys,
                                                       const uint32_t* __restrict__ qsrc, const uint8_t* __restrict__ qright,
-                                                      uint64_t nq, uint64_t chunk, BDyn dy, ovs_route_out* __restrict__ out,
+                                                      uint64_t nq, uint64_t chunk, PersistDyn dy, ovs_route_out* __restrict__ out,
                                                       uint32_t* __restrict__ hopseq, uint32_t* __restrict__ rpcs)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t cursor = wave * chunk;
-    uint64_t end = min(cursor + chunk, dy.ctr ? dy.from : nq);
-    bool more = dy.ctr != nullptr;
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    PersistFeed<K4_TUNE.dyn_chunk> feed(chunk, dy, nq);
     const uint64_t H = (uint64_t)hcm;
 
     bool active = false, local = true, right = false, src_brother = false;
@@ -408,30 +394,15 @@ __global__ __launch_bounds__(256) void k_broose_route(BView V, DelayConsts DC, i
     e.has = 0; e.step = 0; e.right = 0; e.last = NONE;
     e.rk.w[0] = e.rk.w[1] = e.rk.w[2] = e.rk.w[3] = e.rk.w[4] = 0;
     while (true) {
-        const uint64_t need = __ballot(!active);
-        if (more && need != 0 && cursor >= end) {
-            const uint64_t nb = persist_claim_chunk<K4_TUNE.dyn_chunk>(dy.ctr, dy.from, lane);
-            if (nb < nq) {
-                cursor = nb;
-                end = min(nb + (uint64_t)K4_TUNE.dyn_chunk, nq);
-            } else {
-                more = false;
-            }
-        }
-        if (need != 0 && cursor < end) {
-            const uint64_t mine = cursor + (uint64_t)__popcll(need & lt_mask);
-            if (!active && mine < end) {
-                q = mine;
-                active = true;
-                local = true;
-                K = qkeys[q];
-                S = qsrc[q];
-                right = qright[q] != 0;
-                t = 0; hops = 0; ntry = 0; nrpc = 0;
-                vis = vis_bit(S);
-                e.has = 0; e.step = 0; e.right = 0; e.last = NONE;   // the local FindNodeCall carries no extension
-            }
-            cursor += (uint64_t)__popcll(need);
+        if (feed.take(active, dy, nq, q)) {
+            active = true;
+            local = true;
+            K = qkeys[q];
+            S = qsrc[q];
+            right = qright[q] != 0;
+            t = 0; hops = 0; ntry = 0; nrpc = 0;
+            vis = vis_bit(S);
+            e.has = 0; e.step = 0; e.right = 0; e.last = NONE;   // the local FindNodeCall carries no extension
         }
         if (!__any(active)) break;
         if (!active) continue;
@@ -500,37 +471,19 @@ __global__ __launch_bounds__(256) void k_broose_route(BView V, DelayConsts DC, i
             }
         }
         if (fin) {
-            ovs_route_out o;
-            o.hops = (uint16_t)hops;
-            o.status = status;
-            if (status == OVS_LOOKUP_OK) {
-                o.responsible = Rn;
-                o.one_way_hops = (uint8_t)(hops + (Rn != S ? 1 : 0));
-                int64_t lat = t;
-                if (Rn != S) {
-                    // sendRouteMessage to getResult()[0] (BaseOverlay.cc:1107-1146): the closest node the
-                    // sibling knows, not always the sibling itself
-                    double rx = Rc.x, ry = Rc.y;
-                    if (Rn != c) {
-                        const BRec Rr = load_brec(V.rec, Rn);
-                        rx = Rr.x; ry = Rr.y;
-                    }
-                    lat += DC.msgRoute + coord_ns(sx, sy, rx, ry, DC.round);
-                }
-                o.latency_ns = lat;
-            } else {
-                o.responsible = NONE;
-                o.one_way_hops = 0;
-                o.latency_ns = -1;
+            // the route message goes to getResult()[0]: the closest node the sibling knows, not always the
+            // sibling itself
+            double rx = Rc.x, ry = Rc.y;
+            if (status == OVS_LOOKUP_OK && Rn != S && Rn != c) {
+                const BRec Rr = load_brec(V.rec, Rn);
+                rx = Rr.x; ry = Rr.y;
             }
-            out[q] = o;
+            out[q] = iter_route_out(status, hops, t, Rn, S, sx, sy, rx, ry, DC);
             if (rpcs) rpcs[q] = nrpc;
             active = false;
         }
     }
 }
-
-inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 BView make_view(const BrooseTables& t)
 {
@@ -609,7 +562,7 @@ hipError_t broose_route(const BrooseTables& t, const DelayConsts& DC, int hopCou
     if (!hopseq || hopCountMax < 1) return hipErrorInvalidValue;
     using K = PersistKernel<k_broose_route>;
     const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, K4_TUNE);
-    const BDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
     hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, keys, src, right, nq,
                        pl.chunk, dy, out, hopseq, rpcs);
     return hipGetLastError();

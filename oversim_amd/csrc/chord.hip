@@ -1184,8 +1184,6 @@ __global__ void k_delay(const double2* __restrict__ xy, DelayConsts DC, const ui
 // ---------------------------------------------------------------------------
 // host launchers
 
-static inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
 hipError_t launch_check_sorted(const KeyRec* recs, uint32_t n, uint32_t* bad, hipStream_t s)
 {
     if (n < 2) return hipSuccess;

@@ -124,6 +124,8 @@ ovs_status lease_fail(ovs_ctx* c, const char* name, const CachedBuf::Lease& L);
 // ---- the parameters as the kernels take them ----
 // SimTime(double) on the host (identical IEEE double arithmetic to the device path)
 int64_t simtime_host(double seconds, int round);
+// T(L * 8 / datarate): the serialisation time of an L-byte packet
+int64_t bw_host(const ovs_params& P, int32_t bytes);
 int32_t route_bytes(const ovs_params& P);
 DelayConsts delay_consts(const ovs_params& P);
 // the response of a converged n-node ring's LookupCall there and back: min(ns, 1 + successors) NodeHandles
@@ -137,6 +139,12 @@ ovs_status check_chord_route(ovs_ctx* c, const ovs_params& P);
 // host-pointer calls: every lookup's source must be a node of the network (a source past it would
 // be read out of bounds by the lookup kernels); device-pointer calls leave that to the caller (ovs_kbr.h)
 ovs_status check_sources(ovs_ctx* c, const uint32_t* src, uint64_t n, bool dev);
+
+// ---- the visited lists of a batch of single-path iterative lookups (ovs_route.cpp) ----
+// n lists of H responders on stream s.  Without a hop_seq request (*dhop null) they live in the context's
+// cached kvis buffer, unpadded -- the kernels read back only the entries a lookup wrote -- and *dhop becomes
+// its pointer; the caller's own list is set to 0xFF.  The caller releases *vis after the launch.
+ovs_status visited_lists(ovs_ctx* c, uint32_t** dhop, uint64_t n, uint64_t H, hipStream_t s, CachedBuf::Lease* vis);
 
 // ---- the loaders' common steps ----
 // drop the loaded network and everything built on it

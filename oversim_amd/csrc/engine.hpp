@@ -15,6 +15,9 @@ constexpr int KEYBITS = 160;
 // the parts of one device allocation start 256 B apart (host code and the launchers that size work buffers)
 inline uint64_t up256(uint64_t b) { return (b + 255) & ~255ull; }
 
+// blocks of b threads that cover n work items (host: every launcher's grid size)
+inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
+
 // ---------------------------------------------------------------------------
 // Per-launch constants derived from ovs_params on the host.  All times are
 // int64 ns (simtime-scale = -9, default.ini:27).
@@ -78,6 +81,37 @@ __device__ __forceinline__ KeyRec load_rec(const KeyRec* __restrict__ recs, uint
     KeyRec r;
     r.w[0] = a.x; r.w[1] = a.y; r.w[2] = b.x; r.w[3] = b.y; r.w[4] = c.x; r.aux = c.y;
     return r;
+}
+
+// the key of record i (a 64-bit index: rows of records are longer than 2^32 entries)
+__device__ __forceinline__ K160 rkey(const KeyRec* __restrict__ recs, uint64_t i) { return key_of(load_rec(recs + i, 0)); }
+
+// visitOnlyOnce filter: one bit per node hash; a clear bit proves the node unvisited
+__device__ __forceinline__ uint64_t vis_bit(uint32_t x) { return 1ull << ((x * 0x9E3779B1u) >> 26); }
+
+// The ovs_route_out of a finished single-path IterativeLookup under a one-way route (KBRTestApp's one-way test):
+// the lookup took `hops` responders and t ns from source S at (sx, sy).  On OVS_LOOKUP_OK the route message goes
+// to getResult()[0] = `responsible` at (rx, ry) (sendRouteMessage, BaseOverlay.cc:1107-1146, 1240-1258) unless
+// that is the source itself; any other status yields the NONE / 0 / -1 record.  The caller supplies (rx, ry): where
+// the responsible node is not the iteration's responder, its coordinates come from the overlay's own record loader.
+__device__ __forceinline__ ovs_route_out iter_route_out(uint8_t status, int hops, int64_t t, uint32_t responsible, uint32_t S,
+                                                        double sx, double sy, double rx, double ry, const DelayConsts& DC)
+{
+    ovs_route_out o;
+    o.hops = (uint16_t)hops;
+    o.status = status;
+    if (status == OVS_LOOKUP_OK) {
+        o.responsible = responsible;
+        o.one_way_hops = (uint8_t)(hops + (responsible != S ? 1 : 0));
+        int64_t lat = t;
+        if (responsible != S) lat += DC.msgRoute + coord_ns(sx, sy, rx, ry, DC.round);
+        o.latency_ns = lat;
+    } else {
+        o.responsible = NONE;
+        o.one_way_hops = 0;
+        o.latency_ns = -1;
+    }
+    return o;
 }
 
 // ---------------------------------------------------------------------------

@@ -980,8 +980,6 @@ __global__ void k_kad_find_node(KadView V, const uint32_t* __restrict__ node, co
 // ---------------------------------------------------------------------------
 // host side
 
-static inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
 // the level msb(x ^ v) of every sibling x of every node v (sharded networks, KadTables::slev)
 __global__ void k_kad_sib_levels(const KadNode* __restrict__ nodes, const uint32_t* __restrict__ sib, uint32_t n,
                                  int S5, uint8_t* __restrict__ slev)

@@ -113,8 +113,6 @@ __global__ void k_kad_shard_deliver(const typename KadWire<C>::type* __restrict_
     res[o.tag] = r;
 }
 
-inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
 template <bool EX>
 hipError_t kad_mig_step_dispatch(int A, const KadView& V, const DelayConsts& DC, const KadLC& LC, const KadMigStepArgs& a,
                                  int num_cu, hipStream_t s)

@@ -28,8 +28,6 @@ void koorde_free(KoordeTables& t)
 
 namespace {
 
-__device__ __forceinline__ K160 rkey(const KeyRec* __restrict__ recs, uint32_t i) { return key_of(load_rec(recs, i)); }
-
 __device__ __forceinline__ uint32_t ring_add(uint32_t i, uint32_t d, uint32_t n)
 {
     const uint64_t j = (uint64_t)i + d;
@@ -420,9 +418,6 @@ __global__ void k_koorde_build(const KeyRec* __restrict__ recs, uint32_t n, int 
     nd[v] = o;
 }
 
-// visitOnlyOnce filter: one bit per node hash; a clear bit proves the node unvisited
-__device__ __forceinline__ uint64_t vis_bit(uint32_t x) { return 1ull << ((x * 0x9E3779B1u) >> 26); }
-
 #ifndef OVS_KOORDE_WAVES
 #define OVS_KOORDE_WAVES 1
 #endif
@@ -437,18 +432,15 @@ constexpr int KVL = 16;
 // DEF: the default configuration (default.ini: successorListSize 16, shiftingBits 4, useOtherLookup
 // and useSucList on, hopCountMax 50) as compile-time constants -- the start-key arithmetic's
 // modulo by shiftingBits folds to a mask: 5963 -> 4931 static instructions
-// the dynamic tail (persist.hpp; K1's share and chunk): static slices cover [0, from), the rest goes out
-// K3_TUNE.dyn_chunk lookups at a time from the zeroed per-launch counter *ctr (nullptr: static slices only)
-struct KDyn {
-    unsigned long long* ctr;
-    uint64_t from;
-};
+// the dynamic tail (persist.hpp; K1's share and chunk).  The refill below keeps cursor / end / more / lt_mask
+// as locals: with PersistFeed the five instantiations spilled 86 / 126 / 126 / 57 / 55 SGPRs for 78 / 124 /
+// 124 / 56 / 56, one of them a VGPR more, and the record form is pinned at its occupancy (OVS_KOORDE_WAVES)
 constexpr PersistTune K3_TUNE{0.70, 64};
 
 template <bool KR, bool RECORD, bool DEF = false>
 __global__ __launch_bounds__(256, KR ? OVS_KOORDE_WAVES : 1) void k_koorde_route(KView V0, const double2* __restrict__ xy, DelayConsts DC, int hcm0,
                                                       const K160* __restrict__ qkeys, const uint32_t* __restrict__ qsrc,
-                                                      uint64_t nq, uint64_t chunk, KDyn dy, ovs_route_out* __restrict__ out,
+                                                      uint64_t nq, uint64_t chunk, PersistDyn dy, ovs_route_out* __restrict__ out,
                                                       uint32_t* __restrict__ hopseq, uint32_t* __restrict__ rpcs)
 {
     const int lane = threadIdx.x & 63;
@@ -575,24 +567,8 @@ __global__ __launch_bounds__(256, KR ? OVS_KOORDE_WAVES : 1) void k_koorde_route
             }
         }
         if (fin) {
-            ovs_route_out o;
-            o.hops = (uint16_t)hops;
-            o.status = status;
-            if (status == OVS_LOOKUP_OK) {
-                o.responsible = R;
-                o.one_way_hops = (uint8_t)(hops + (R != S ? 1 : 0));
-                int64_t lat = t;
-                if (R != S) {
-                    // sendRouteMessage to the result (BaseOverlay.cc:1107-1146): R is this iteration's c
-                    lat += DC.msgRoute + coord_ns(sx, sy, cx, cy, DC.round);
-                }
-                o.latency_ns = lat;
-            } else {
-                o.responsible = NONE;
-                o.one_way_hops = 0;
-                o.latency_ns = -1;
-            }
-            out[q] = o;
+            // the route message goes to the result: R is this iteration's c
+            out[q] = iter_route_out(status, hops, t, R, S, sx, sy, cx, cy, DC);
             // FindNodeCalls sent: one per accepted responder, plus a call to c whose response did
             // not count (its findNode threw, it timed out, or it came after the lookup timeout)
             const bool lost = c != S && (status == OVS_LOOKUP_BROKEN || status == OVS_LOOKUP_RPC_TIMEOUT ||
@@ -622,8 +598,6 @@ __global__ void k_koorde_find_node(KView V, const uint32_t* __restrict__ node, c
     next[i] = h;
     if (h != NONE) ext[i] = e;
 }
-
-inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 KView make_view(const KoordeTables& t, const KeyRec* recs)
 {
@@ -672,7 +646,7 @@ hipError_t koorde_route(const KoordeTables& t, const KeyRec* recs, const double2
     auto launch = [&](auto k) {
         using K = decltype(k);
         const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, K3_TUNE);
-        const KDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+        const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
         hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, kv, xy, DC, hopCountMax, keys, src, nq,
                            pl.chunk, dy, out, hopseq, rpcs);
     };

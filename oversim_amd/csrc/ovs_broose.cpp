@@ -29,7 +29,7 @@ int32_t packet_bytes(int32_t bits) { return (bits + 7) / 8 + 28; }
 DelayConsts broose_delay_consts(const ovs_params& P)
 {
     DelayConsts d = delay_consts(P);
-    auto bw = [&](int32_t bytes) { return simtime_host((double)((int64_t)bytes * 8) / P.datarate, P.simtimeRound); };
+    auto bw = [&](int32_t bytes) { return bw_host(P, bytes); };
     const int32_t ext = 160 + 8 + 1 + 208;
     d.callBytes = packet_bytes(440 + ext);                                         // FINDNODECALL_L
     const int32_t resp1 = packet_bytes(264 + 208 + ext + (P.measureAuthBlock ? 800 : 0));   // FINDNODERESPONSE_L, one NodeHandle
@@ -218,16 +218,8 @@ ovs_status ovs_broose_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint
     uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
     uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
     if (!F.ok()) return frame_fail(c, F);
-    // without a hop_seq request the visited lists live in the context's cached buffer, unpadded: the
-    // kernel reads back only the entries a lookup wrote
     CachedBuf::Lease vis;
-    if (!dhop) {
-        vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
-        if (!vis) return lease_fail(c, "kvis", vis);
-        dhop = reinterpret_cast<uint32_t*>(vis.data());
-    } else {
-        HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
-    }
+    if ((st = visited_lists(c, &dhop, n, H, s, &vis)) != OVS_OK) return st;
     const DynSlots::Lease dyn = dyn_acquire(c, n, s);
     const hipError_t e = broose_route(c->broose, broose_delay_consts(P), P.hopCountMax, dk, ds, dr, n, dout, dhop, drpc, c->num_cu, s,
                                       dyn.get());

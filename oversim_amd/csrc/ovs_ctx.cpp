@@ -110,6 +110,11 @@ int64_t simtime_host(double seconds, int round)
     return round ? (int64_t)std::floor(x + 0.5) : (int64_t)x;
 }
 
+int64_t bw_host(const ovs_params& P, int32_t bytes)
+{
+    return simtime_host((double)((int64_t)bytes * 8) / P.datarate, P.simtimeRound);
+}
+
 int32_t route_bytes(const ovs_params& P)
 {
     // BASEROUTE_L 424 bits + BASEAPPDATA_L 40 bits + KBRTestMessage payload + UDP/IP 28 B
@@ -121,7 +126,7 @@ DelayConsts delay_consts(const ovs_params& P)
 {
     DelayConsts d{};
     d.round = P.simtimeRound;
-    auto bw = [&](int32_t bytes) { return simtime_host((double)((int64_t)bytes * 8) / P.datarate, P.simtimeRound); };
+    auto bw = [&](int32_t bytes) { return bw_host(P, bytes); };
     const int64_t acc = simtime_host(P.accessDelay, P.simtimeRound);
     d.access2 = 2 * acc;
     d.callBytes = 83;        // FINDNODECALL_L 440 bits + 28 B

@@ -28,7 +28,7 @@ ovs_status load_begin(ovs_ctx* c, const ovs_pastry_params* bp, const ovs_key160*
 DelayConsts pastry_iter_delay_consts(const ovs_params& P)
 {
     DelayConsts d = delay_consts(P);     // measureAuthBlock is in respBase
-    auto bw = [&](int32_t bytes) { return simtime_host((double)((int64_t)bytes * 8) / P.datarate, P.simtimeRound); };
+    auto bw = [&](int32_t bytes) { return bw_host(P, bytes); };
     d.callBytes += 28;
     d.respBase += 28;
     d.msgCall = 2 * bw(d.callBytes) + d.access2;
@@ -71,16 +71,8 @@ ovs_status pastry_iter_call(ovs_ctx* c, const char* name, bool route, const ovs_
     uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
     uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
     if (!F.ok()) return frame_fail(c, F);
-    // without a hop_seq request the visited lists live in the context's cached buffer, unpadded: the
-    // kernel reads back only the entries a lookup wrote
     CachedBuf::Lease vis;
-    if (!dhop) {
-        vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
-        if (!vis) return lease_fail(c, "kvis", vis);
-        dhop = reinterpret_cast<uint32_t*>(vis.data());
-    } else {
-        HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
-    }
+    if ((st = visited_lists(c, &dhop, n, H, s, &vis)) != OVS_OK) return st;
     const DynSlots::Lease dyn = dyn_acquire(c, n, s);
     const hipError_t e = pastry_iter(c->pastry, pastry_iter_delay_consts(P), P.hopCountMax, ns, dk, ds, n, dro, dlo, dsib, dhop, drpc,
                                      c->num_cu, s, dyn.get());

@@ -168,6 +168,18 @@ ovs_status route_check(ovs_ctx* c, const ovs_params& P, hipStream_t s)
     return OVS_OK;
 }
 
+ovs_status visited_lists(ovs_ctx* c, uint32_t** dhop, uint64_t n, uint64_t H, hipStream_t s, CachedBuf::Lease* vis)
+{
+    if (*dhop) {
+        HIPCHK(c, hipMemsetAsync(*dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+        return OVS_OK;
+    }
+    *vis = c->kvis.acquire(sizeof(uint32_t) * n * H, s);
+    if (!*vis) return lease_fail(c, "kvis", *vis);
+    *dhop = reinterpret_cast<uint32_t*>(vis->data());
+    return OVS_OK;
+}
+
 ovs_status route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
                         ovs_route_out* dout, uint32_t* dhop, uint32_t* drpc, hipStream_t s)
 {

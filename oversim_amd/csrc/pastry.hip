@@ -28,8 +28,6 @@ void pastry_free(PastryTables& t)
 
 namespace {
 
-__device__ __forceinline__ K160 rkey(const KeyRec* __restrict__ recs, uint64_t i) { return key_of(load_rec(recs + i, 0)); }
-
 // ---------------------------------------------------------------------------
 // the converged tables
 
@@ -166,22 +164,13 @@ __global__ void k_pastry_find_node(PView V, const uint32_t* __restrict__ node, c
 // ---------------------------------------------------------------------------
 // the route
 
-struct PDyn {
-    unsigned long long* ctr;
-    uint64_t from;
-};
 constexpr PersistTune KP_TUNE{0.70, 64};
 
 __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, int hcm, int nred, const K160* __restrict__ qkeys,
-                                                      const uint32_t* __restrict__ qsrc, uint64_t nq, uint64_t chunk, PDyn dy,
+                                                      const uint32_t* __restrict__ qsrc, uint64_t nq, uint64_t chunk, PersistDyn dy,
                                                       ovs_route_out* __restrict__ out, uint32_t* __restrict__ hopseq)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t cursor = wave * chunk;
-    uint64_t end = min(cursor + chunk, dy.ctr ? dy.from : nq);
-    bool more = dy.ctr != nullptr;
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    PersistFeed<KP_TUNE.dyn_chunk> feed(chunk, dy, nq);
     const uint64_t H = (uint64_t)max(hcm, 1);
 
     bool active = false, local = true;
@@ -193,29 +182,14 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
     int64_t t = 0;
     int hops = 0;
     while (true) {
-        const uint64_t need = __ballot(!active);
-        if (more && need != 0 && cursor >= end) {
-            const uint64_t nb = persist_claim_chunk<KP_TUNE.dyn_chunk>(dy.ctr, dy.from, lane);
-            if (nb < nq) {
-                cursor = nb;
-                end = min(nb + (uint64_t)KP_TUNE.dyn_chunk, nq);
-            } else {
-                more = false;
-            }
-        }
-        if (need != 0 && cursor < end) {
-            const uint64_t mine = cursor + (uint64_t)__popcll(need & lt_mask);
-            if (!active && mine < end) {
-                q = mine;
-                active = true;
-                local = true;
-                K = qkeys[q];
-                S = qsrc[q];
-                cur = S;
-                last = NONE;
-                t = 0; hops = 0;
-            }
-            cursor += (uint64_t)__popcll(need);
+        if (feed.take(active, dy, nq, q)) {
+            active = true;
+            local = true;
+            K = qkeys[q];
+            S = qsrc[q];
+            cur = S;
+            last = NONE;
+            t = 0; hops = 0;
         }
         if (!__any(active)) break;
         if (!active) continue;
@@ -287,17 +261,12 @@ __device__ uint32_t source_entry(const PView& V, uint32_t S, const K160& K, int 
 // its bits are in DC); iterativeJoinHook (Pastry.cc:591-614) only counts joinHopCount in it for a lookup that is
 // no join and changes no answer, so nothing of it is carried.
 __global__ __launch_bounds__(256) void k_pastry_iter(PView V, DelayConsts DC, int hcm, int nsib, const K160* __restrict__ qkeys,
-                                                     const uint32_t* __restrict__ qsrc, uint64_t nq, uint64_t chunk, PDyn dy,
+                                                     const uint32_t* __restrict__ qsrc, uint64_t nq, uint64_t chunk, PersistDyn dy,
                                                      ovs_route_out* __restrict__ rout, ovs_lookup_out* __restrict__ lout,
                                                      uint32_t* __restrict__ sibs, uint32_t* __restrict__ hopseq,
                                                      uint32_t* __restrict__ rpcs)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t cursor = wave * chunk;
-    uint64_t end = min(cursor + chunk, dy.ctr ? dy.from : nq);
-    bool more = dy.ctr != nullptr;
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    PersistFeed<KP_TUNE.dyn_chunk> feed(chunk, dy, nq);
     const uint64_t H = (uint64_t)hcm;
 
     bool active = false, local = true, srcvec = false;
@@ -309,29 +278,14 @@ __global__ __launch_bounds__(256) void k_pastry_iter(PView V, DelayConsts DC, in
     int64_t t = 0;
     int hops = 0, ntry = 0, ndead = 0;
     while (true) {
-        const uint64_t need = __ballot(!active);
-        if (more && need != 0 && cursor >= end) {
-            const uint64_t nb = persist_claim_chunk<KP_TUNE.dyn_chunk>(dy.ctr, dy.from, lane);
-            if (nb < nq) {
-                cursor = nb;
-                end = min(nb + (uint64_t)KP_TUNE.dyn_chunk, nq);
-            } else {
-                more = false;
-            }
-        }
-        if (need != 0 && cursor < end) {
-            const uint64_t mine = cursor + (uint64_t)__popcll(need & lt_mask);
-            if (!active && mine < end) {
-                q = mine;
-                active = true;
-                local = true;
-                srcvec = false;
-                K = qkeys[q];
-                S = qsrc[q];
-                cur = S;
-                t = 0; hops = 0; ntry = 0; ndead = 0; nrpc = 0;
-            }
-            cursor += (uint64_t)__popcll(need);
+        if (feed.take(active, dy, nq, q)) {
+            active = true;
+            local = true;
+            srcvec = false;
+            K = qkeys[q];
+            S = qsrc[q];
+            cur = S;
+            t = 0; hops = 0; ntry = 0; ndead = 0; nrpc = 0;
         }
         if (!__any(active)) break;
         if (!active) continue;
@@ -430,30 +384,14 @@ __global__ __launch_bounds__(256) void k_pastry_iter(PView V, DelayConsts DC, in
             if (sv)
                 for (int j = cnt; j < nsib; ++j) sv[j] = NONE;
             if (rout) {
-                ovs_route_out o;
-                o.hops = (uint16_t)hops;
-                o.status = status;
-                if (ok) {
-                    o.responsible = Rn;
-                    o.one_way_hops = (uint8_t)(hops + (Rn != S ? 1 : 0));
-                    int64_t lat = t;
-                    if (Rn != S) {
-                        // sendRouteMessage to getResult()[0] (BaseOverlay.cc:1253-1257): the closest node the last
-                        // responder knows, not always that responder
-                        double rx = Rc.x, ry = Rc.y;
-                        if (Rn != cur) {
-                            const PRec Rr = load_prec(V.rec, Rn);
-                            rx = Rr.x; ry = Rr.y;
-                        }
-                        lat += DC.msgRoute + coord_ns(sx, sy, rx, ry, DC.round);
-                    }
-                    o.latency_ns = lat;
-                } else {
-                    o.responsible = NONE;
-                    o.one_way_hops = 0;
-                    o.latency_ns = -1;
+                // the route message goes to getResult()[0]: the closest node the last responder knows, not always
+                // that responder
+                double rx = Rc.x, ry = Rc.y;
+                if (ok && Rn != S && Rn != cur) {
+                    const PRec Rr = load_prec(V.rec, Rn);
+                    rx = Rr.x; ry = Rr.y;
                 }
-                rout[q] = o;
+                rout[q] = iter_route_out(status, hops, t, Rn, S, sx, sy, rx, ry, DC);
             } else {
                 ovs_lookup_out o;
                 o.num_siblings = (uint32_t)cnt;
@@ -468,8 +406,6 @@ __global__ __launch_bounds__(256) void k_pastry_iter(PView V, DelayConsts DC, in
         }
     }
 }
-
-inline unsigned nblk(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 hipError_t alloc_tables(uint32_t n, const PastryShape& sh, int rows, PastryTables& t)
 {
@@ -579,7 +515,7 @@ hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCou
     if (nq == 0) return hipSuccess;
     using K = PersistKernel<k_pastry_route>;
     const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
-    const PDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
     hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, recNumRedundantNodes, keys,
                        src, nq, pl.chunk, dy, out, hopseq);
     return hipGetLastError();
@@ -595,7 +531,7 @@ hipError_t pastry_iter(const PastryTables& t, const DelayConsts& DC, int hopCoun
         return hipErrorInvalidValue;
     using K = PersistKernel<k_pastry_iter>;
     const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
-    const PDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
     hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, numSiblings, keys, src, nq,
                        pl.chunk, dy, rout, lout, siblings, hopseq, rpcs);
     return hipGetLastError();

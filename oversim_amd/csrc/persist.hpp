@@ -1,21 +1,24 @@
 // persist.hpp -- the persistent-slice scheduler shared by the lane-refill route kernels: K1
-// (k_chord_lanes, chord.hip), K2 (k_kad_route, kad_route.hip), K2x (k_kad_refresh, kad_refresh.hip)
-// and K3 (k_koorde_route, koorde.hip).
+// (k_chord_lanes, chord.hip), K2 (k_kad_route, kad_route.hip), K2x (k_kad_refresh, kad_refresh.hip),
+// K3 (k_koorde_route, koorde.hip), K4 (k_broose_route, broose.hip) and the two Pastry kernels
+// (k_pastry_route, k_pastry_iter, pastry.hip).
 //
 // Each launches an occupancy-sized persistent grid and gives every wave one contiguous static slice
 // of the batch; a lane whose lookup ended takes the wave's next one by ballot + popcount (the
-// kernel's own refill body).  Persistent waves finish their static slices up to a quarter of the
-// kernel apart (the tail census below), so with a zeroed per-launch counter the static slices cover
-// only a share of the batch and the rest goes out in chunks of a few lookups, one atomic a chunk:
-// the waves that run ahead take more (the dynamic tail).  The share and the chunk are per-kernel
-// tunables (PersistTune), kept next to their kernels.
+// refill).  Persistent waves finish their static slices up to a quarter of the
+// kernel apart (the tail census below), so with a zeroed per-launch counter (PersistDyn) the static
+// slices cover only a share of the batch and the rest goes out in chunks of a few lookups, one atomic
+// a chunk: the waves that run ahead take more (the dynamic tail).  The share and the chunk are
+// per-kernel tunables (PersistTune), kept next to their kernels.
 //
 // The plan (persist_plan) is plain C++: it compiles without a HIP compiler
-// (tests/persist_plan_driver.cpp).  The occupancy query and the tail census need one (__HIPCC__).
-// On the device the claim of the next dynamic chunk is persist_claim_chunk; a wave's cursor / end /
-// more stay locals of each kernel's refill: as members of a shared slice object they compiled to
-// different register allocations (K1's shard step +18 spilled SGPRs, K2 and K2x a few spilled
-// VGPRs more or fewer), and these kernels sit at their occupancy limits.
+// (tests/persist_plan_driver.cpp).  The occupancy query, the refill and the tail census need one
+// (__HIPCC__).  On the device the refill is stated once, PersistFeed<CH>::take: K4 and the two Pastry
+// kernels, which are untuned, run it.  K1, K2, K2x and K3 keep cursor / end / more / lt_mask as
+// locals of their own loops and share only the claim of the next dynamic chunk, persist_claim_chunk:
+// as members of a shared object these compiled to different register allocations (K1's shard step
+// +18 spilled SGPRs, K2 and K2x a few spilled VGPRs more or fewer; K3: see koorde.hip), and these
+// kernels sit at their occupancy limits.
 #pragma once
 
 #include <cstdint>
@@ -103,8 +106,7 @@ uint64_t persist_waves(int num_cu)
 // The claim of a wave's next dynamic chunk: lane 0 adds CH to the launch's counter (one atomic a
 // chunk), and the chunk's first lookup, dyn_from + the counter's old value, comes back wave-uniform.
 // The caller, a wave whose slice is spent, takes [nb, min(nb + CH, n)) when nb < n; otherwise the
-// batch is handed out.  It returns a value only: cursor / end / more stay the kernel's own locals,
-// so nothing new is live across the kernel's loop
+// batch is handed out.  It returns a value only, so nothing new is live across a kernel's loop
 template <uint32_t CH>
 __device__ __forceinline__ uint64_t persist_claim_chunk(unsigned long long* ctr, uint64_t dyn_from, int lane)
 {
@@ -113,6 +115,62 @@ __device__ __forceinline__ uint64_t persist_claim_chunk(unsigned long long* ctr,
     return dyn_from + (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
                        (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)b));
 }
+
+// the per-launch counter of the dynamic tail: static slices cover [0, from), the rest goes out a chunk
+// at a time from the zeroed counter *ctr (nullptr: static slices only)
+struct PersistDyn {
+    unsigned long long* ctr;
+    uint64_t from;
+};
+
+// A wave's feed of lookups: its static slice [wave * chunk, (wave + 1) * chunk) cut at the end of the
+// static region, then dynamic chunks of CH lookups while the batch lasts.  A kernel's loop head reads
+//     if (feed.take(active, dy, nq, q)) { active = true; /* the kernel's own per-lookup init */ }
+//     if (!__any(active)) break;
+//     if (!active) continue;
+template <uint32_t CH>
+struct PersistFeed {
+    uint64_t cursor, end;
+    bool more;                 // dynamic chunks may be left
+    uint64_t lt_mask;          // the lanes below this one
+
+    __device__ __forceinline__ PersistFeed(uint64_t chunk, const PersistDyn& dy, uint64_t nq)
+    {
+        const int lane = threadIdx.x & 63;
+        const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+        cursor = wave * chunk;
+        end = min(cursor + chunk, dy.ctr ? dy.from : nq);
+        more = dy.ctr != nullptr;
+        lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    }
+
+    // Wave-uniform call.  The idle lanes (ballot) take the next lookups of the slice in lane order; a
+    // spent slice is first replaced by a new dynamic chunk.  True where this lane was idle and now has
+    // lookup q.
+    __device__ __forceinline__ bool take(bool active, const PersistDyn& dy, uint64_t nq, uint64_t& q)
+    {
+        const uint64_t need = __ballot(!active);
+        if (more && need != 0 && cursor >= end) {
+            const uint64_t nb = persist_claim_chunk<CH>(dy.ctr, dy.from, threadIdx.x & 63);
+            if (nb < nq) {
+                cursor = nb;
+                end = min(nb + (uint64_t)CH, nq);
+            } else {
+                more = false;
+            }
+        }
+        bool taken = false;
+        if (need != 0 && cursor < end) {
+            const uint64_t mine = cursor + (uint64_t)__popcll(need & lt_mask);
+            if (!active && mine < end) {
+                q = mine;
+                taken = true;
+            }
+            cursor += (uint64_t)__popcll(need);
+        }
+        return taken;
+    }
+};
 
 // tail census (-DOVS_K1_TAIL / -DOVS_KAD_TAIL builds): each persistent wave's exit on the 100 MHz
 // real-time clock, so the spread of the waves' finishing times (the kernel's tail) can be read off

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from oversim_amd import KbrEngine, Params, workload as W
+from oversim_amd import BrooseParams, KbrEngine, Params, PastryParams, workload as W
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +54,7 @@ def test_concurrent_streams_share_no_counter(engine: KbrEngine, overlay, monkeyp
 
 
 # 3 * 2^18 + 37 lookups: at most 8 blocks of 4 waves fit on a CU, so with 256 CUs a static slice of
-# 0.70 * n / (256 * 8 * 4) = 67 lookups holds K1's and K3's 64-lookup chunk (and K2's 32) whatever the
+# 0.70 * n / (256 * 8 * 4) = 67 lookups holds the 64-lookup chunk of K1, K3, K4 and the Pastry kernels (and K2's 32) whatever the
 # kernels' occupancy -- the tail is on -- and the dynamic region is no multiple of the chunk: the last
 # chunk handed out is partial
 N_PARTIAL = 3 * (1 << 18) + 37
@@ -94,6 +94,38 @@ def test_koorde_tail_equals_static(engine: KbrEngine, monkeypatch):
     engine.koorde_load(net.ids, net.xy)
     keys, src = W.lookups(net.ids, N_PARTIAL, 105, node_ids=False)
     ref, got = _static_and_dynamic(monkeypatch, lambda: engine.lookup(keys, src))
+    _assert_same(ref, got)
+
+
+def test_broose_tail_equals_static(engine: KbrEngine, monkeypatch):
+    net = W.population(1 << 12, 94)
+    engine.set_params(Params.broose())
+    engine.broose_load(net.ids, net.xy, BrooseParams.default())
+    keys, src = W.lookups(net.ids, N_PARTIAL, 107, node_ids=False)
+    right = (np.arange(N_PARTIAL) & 1).astype(np.uint8)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.broose_lookup(keys, src, right, record_hops=True, count_rpcs=True))
+    _assert_same(ref, got)
+
+
+def test_pastry_tail_equals_static(engine: KbrEngine, monkeypatch):
+    net = W.population(1 << 12, 95)
+    engine.set_params(Params.pastry())
+    engine.pastry_load(net.ids, net.xy, PastryParams.default(routeMsgAcks=0))
+    keys, src = W.lookups(net.ids, N_PARTIAL, 108, node_ids=False)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.pastry_lookup(keys, src, record_hops=True))
+    _assert_same(ref, got)
+
+
+def test_pastry_iter_tail_equals_static(engine: KbrEngine, monkeypatch):
+    """k_pastry_iter in both of its forms: the LookupCall with 4 siblings and the one-way route, which needs
+    routeMsgAcks off."""
+    net = W.population(1 << 12, 96)
+    engine.set_params(Params.pastry().replace(routingType=0))
+    engine.pastry_load(net.ids, net.xy, PastryParams.default(routeMsgAcks=0))
+    keys, src = W.lookups(net.ids, N_PARTIAL, 109, node_ids=False)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.pastry_lookup_call(keys, src, 4, record_hops=True))
+    _assert_same(ref, got)
+    ref, got = _static_and_dynamic(monkeypatch, lambda: engine.pastry_iterative_lookup(keys, src, record_hops=True))
     _assert_same(ref, got)
 
 
