@@ -1304,9 +1304,10 @@ ovs_status  ovs_broose_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const u
  * per-hop acks, and iterative lookups (routingType 0: ovs_pastry_lookup_batch, ovs_pastry_iterative_route_batch
  * below).  Refused with OVS_ENOTSUP: routeMsgAcks, numberOfNeighbors != 0, bitsPerDigit outside 1..4,
  * odd numberOfLeaves or above 32, the full-recursive and source-routing types.  Of the application tiers Scribe runs on a
- * Pastry context built by ovs_pastry_load (ovs_scribe_*, OVS_HAS_SCRIBE_PASTRY).  Everything else on one --
+ * Pastry context built by ovs_pastry_load (ovs_scribe_*, OVS_HAS_SCRIBE_PASTRY) and the overlay broadcast on one
+ * from either loader (ovs_pastry_broadcast_batch, OVS_HAS_PASTRY_BROADCAST).  Everything else on one --
  * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, every other application tier -- is refused with
- * OVS_ENOTSUP. */
+ * OVS_ENOTSUP (ovs_chord_broadcast_batch, which names its overlay: OVS_ESTATE). */
 #define OVS_HAS_PASTRY 1
 enum { OVS_OVERLAY_PASTRY = 6 };
 typedef struct ovs_pastry_params {
@@ -1388,6 +1389,34 @@ ovs_status  ovs_pastry_lookup_batch(ovs_ctx* ctx, const ovs_key160* keys, const 
                                     uint32_t* rpcs, uint32_t flags, void* stream);
 ovs_status  ovs_pastry_iterative_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
                                              ovs_route_out* out, uint32_t* hop_seq, uint32_t flags, void* stream);
+
+/* ---- Pastry overlay broadcast (additive to ABI 12; test OVS_HAS_PASTRY_BROADCAST) ----
+ * Replaces, for a batch of broadcasts on a Pastry context from either loader (ovs_pastry_load,
+ * ovs_pastry_load_tables):
+ *   BroadcastTestApp::initBroadcast / rpcBroadcastRequest  src/tier2/broadcasttestapp/BroadcastTestApp.cc:197-340
+ *   Pastry::forwardBroadcast                                src/overlay/pastry/Pastry.cc:1343-1390
+ *   SimpleNodeEntry::calcDelay with the sender's transmit queue  SimpleNodeEntry.cc:164-194
+ * the reference's [Config PastryBroadcast].  A node that receives the request with TTL > 0 and limit l (the
+ * initiator: 0) sends a request with TTL - 1 and limit row + 1 to every entry of its routing-table rows
+ * l .. getLastRow() - 1 that is neither empty nor itself, by row and then by column; the j-th of them leaves
+ * after j + 1 serialisation times.  The requests go to nodes, straight over UDP (BaseOverlay.cc:1340-1341), so
+ * routingType and routeMsgAcks do not enter: every value of either runs.  The PastryBroadcastInfo object adds
+ * nothing to a call's length, so lengths, messages and bytes are ovs_chord_broadcast_batch's.  A table slot
+ * (r, c) holds a node that shares r digits with its owner and has digit c at r -- the rule builds that, the
+ * explicit loader checks it -- so no node is reached twice; on explicit tables with empty slots the nodes
+ * behind them are not reached (arrival_ns -1, stats.actual + stats.expired < stats.expected).  No DHT items
+ * are stored (no BroadcastResponseCall), no request times out, no midpoint request exists (Pastry.cc:1367
+ * makes 1374-1381 dead code).
+ *
+ * Arguments, pointer modes, completion and the OVS_EINVAL cases are ovs_chord_broadcast_batch's; records and
+ * statistics are ovs_bcast_node and ovs_bcast_stats.  OVS_ENOTSUP: rows * (2^bitsPerDigit - 1) requests of
+ * this length exceed the default sendQueueLength of 1 MB (default.ini:553) in one node's transmit queue, where
+ * the reference drops and this engine does not; with an empty query no table reaches it.  OVS_ESTATE: another
+ * overlay's context or no network. */
+#define OVS_HAS_PASTRY_BROADCAST 1
+ovs_status  ovs_pastry_broadcast_batch(ovs_ctx* ctx, const uint32_t* initiators, uint64_t nb, int32_t ttl,
+                                       int32_t query_bytes, ovs_bcast_node* nodes, ovs_bcast_stats* stats,
+                                       uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

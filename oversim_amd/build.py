@@ -34,7 +34,7 @@ CFLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
     "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value", "-Wno-bitwise-instead-of-logical",
 ]
-SOURCES = ["chord.hip", "chord_bcast.hip", "compact.hip", "dht.hip", "dht_teams.hip", "scribe.hip", "epichord.hip", "ksort.hip", "kad.hip", "kad_general.hip", "kad_refresh.hip", "kad_route.hip", "kad_shard.hip", "kbr_rpc.hip", "koorde.hip", "broose.hip", "pastry.hip", "stats.hip", "ovs_ctx.cpp", "ovs_load.cpp", "ovs_shard.cpp", "ovs_route.cpp", "ovs_kad_maint.cpp", "shard_route.cpp",
+SOURCES = ["chord.hip", "chord_bcast.hip", "compact.hip", "dht.hip", "dht_teams.hip", "scribe.hip", "epichord.hip", "ksort.hip", "kad.hip", "kad_general.hip", "kad_refresh.hip", "kad_route.hip", "kad_shard.hip", "kbr_rpc.hip", "koorde.hip", "broose.hip", "pastry.hip", "pastry_bcast.hip", "stats.hip", "ovs_ctx.cpp", "ovs_load.cpp", "ovs_shard.cpp", "ovs_route.cpp", "ovs_kad_maint.cpp", "shard_route.cpp",
            "ovs_broose.cpp", "ovs_pastry.cpp", "app_kbrtest.cpp", "app_dht.cpp", "app_dht_teams.cpp", "app_bcast.cpp", "app_scribe.cpp", "ovs_ini.cpp", "host_tables.cpp"]
 # translation units compiled more than once: (source, object stem, extra flags).  K2 is built per
 # (alpha, exact) pair so its instantiations compile in parallel; A = 8 serves alpha 5..8 (A is the

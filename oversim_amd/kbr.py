@@ -463,6 +463,7 @@ def lib() -> C.CDLL:
         "ovs_delay_batch": ([vp, vp, vp, vp, u64, vp, u32, vp], C.c_int),
         "ovs_sync": ([vp], C.c_int),
         "ovs_chord_broadcast_batch": ([vp, vp, u64, i32, i32, vp, vp, u32, vp], C.c_int),
+        "ovs_pastry_broadcast_batch": ([vp, vp, u64, i32, i32, vp, vp, u32, vp], C.c_int),
         "ovs_kbrtest_stats_batch": ([vp, vp, vp, vp, u64, C.c_double, i32, vp, u32, vp], C.c_int),
         "ovs_chord_fix_fingers": ([vp, vp, u64, vp], C.c_int),
         "ovs_lookup_batch": ([vp, vp, vp, u64, i32, vp, vp, u32, vp], C.c_int),
@@ -1265,28 +1266,46 @@ class KbrEngine:
                   "ovs_delay_batch")
         return out
 
+    def _broadcast(self, call: str, initiators, ttl: int, query_bytes: int, nodes: bool):
+        init = np.ascontiguousarray(initiators, dtype=np.uint32)
+        nb = len(init)
+        rec = np.empty((nb, self.n), dtype=BCAST_NODE_DTYPE) if nodes else None
+        st = (BcastStats * max(nb, 1))()
+        self._chk(getattr(self._L, call)(self._h, _ptr(init), nb, int(ttl), int(query_bytes), _ptr(rec),
+                                         C.cast(st, C.c_void_p), 0, None), call)
+        return rec, [bcast_stats_dict(st[b]) for b in range(nb)]
+
+    def _broadcast_device(self, call: str, init_ptr: int, nb: int, ttl: int, query_bytes: int, nodes_ptr: int | None,
+                          stream: int | None):
+        st = (BcastStats * max(nb, 1))()
+        self._chk(getattr(self._L, call)(self._h, C.c_void_p(init_ptr), nb, int(ttl), int(query_bytes),
+                                         C.c_void_p(nodes_ptr) if nodes_ptr else None, C.cast(st, C.c_void_p), DEVICE_PTRS,
+                                         C.c_void_p(stream) if stream else None), call)
+        return [bcast_stats_dict(st[b]) for b in range(nb)]
+
     def chord_broadcast(self, initiators, ttl: int = 100, query_bytes: int = 0, nodes: bool = True):
         """Batched overlay broadcasts on a converged Chord ring (ovs_chord_broadcast_batch:
         BroadcastTestApp::rpcBroadcastRequest over Chord::forwardBroadcast, Chord.cc:1410-1445), one
         from each initiator.  Returns (records, stats): records (nb, n) of BCAST_NODE_DTYPE (None with
         nodes=False) and one dict per broadcast (ovs_bcast_stats; hop_count = the cStdDev fields)."""
-        init = np.ascontiguousarray(initiators, dtype=np.uint32)
-        nb = len(init)
-        rec = np.empty((nb, self.n), dtype=BCAST_NODE_DTYPE) if nodes else None
-        st = (BcastStats * max(nb, 1))()
-        self._chk(self._L.ovs_chord_broadcast_batch(self._h, _ptr(init), nb, int(ttl), int(query_bytes), _ptr(rec),
-                                                    C.cast(st, C.c_void_p), 0, None), "ovs_chord_broadcast_batch")
-        return rec, [bcast_stats_dict(st[b]) for b in range(nb)]
+        return self._broadcast("ovs_chord_broadcast_batch", initiators, ttl, query_bytes, nodes)
 
     def chord_broadcast_device(self, init_ptr: int, nb: int, ttl: int, query_bytes: int, nodes_ptr: int | None,
                                stream: int | None = None):
         """The same for device-resident initiators / records (the call completes on `stream`); returns the stats."""
-        st = (BcastStats * max(nb, 1))()
-        self._chk(self._L.ovs_chord_broadcast_batch(self._h, C.c_void_p(init_ptr), nb, int(ttl), int(query_bytes),
-                                                    C.c_void_p(nodes_ptr) if nodes_ptr else None,
-                                                    C.cast(st, C.c_void_p), DEVICE_PTRS,
-                                                    C.c_void_p(stream) if stream else None), "ovs_chord_broadcast_batch")
-        return [bcast_stats_dict(st[b]) for b in range(nb)]
+        return self._broadcast_device("ovs_chord_broadcast_batch", init_ptr, nb, ttl, query_bytes, nodes_ptr, stream)
+
+    def pastry_broadcast(self, initiators, ttl: int = 100, query_bytes: int = 0, nodes: bool = True):
+        """Batched overlay broadcasts on a Pastry context from either loader (ovs_pastry_broadcast_batch:
+        BroadcastTestApp::rpcBroadcastRequest over Pastry::forwardBroadcast, Pastry.cc:1343-1390), one from
+        each initiator.  Returns what chord_broadcast returns; on explicit tables with empty slots the nodes
+        behind them stay unreached (arrival_ns -1)."""
+        return self._broadcast("ovs_pastry_broadcast_batch", initiators, ttl, query_bytes, nodes)
+
+    def pastry_broadcast_device(self, init_ptr: int, nb: int, ttl: int, query_bytes: int, nodes_ptr: int | None,
+                                stream: int | None = None):
+        """The same for device-resident initiators / records (the call completes on `stream`); returns the stats."""
+        return self._broadcast_device("ovs_pastry_broadcast_batch", init_ptr, nb, ttl, query_bytes, nodes_ptr, stream)
 
     # -- Scribe
     def scribe_build(self, group_keys, member_group, member_node, capacity: int | None = None):
