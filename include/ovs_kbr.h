@@ -634,7 +634,8 @@ ovs_status  ovs_kbrtest_rpc_stats_batch(ovs_ctx* ctx, const ovs_rpc_out* out, co
  * ordered UNSPECIFIED_VALUE first, then by ascending token.
  * Accepted: what ovs_lookup_batch accepts with routingType iterative and lookupParallelRpcs = 1 on an
  * unsharded Chord or Kademlia network (the source then never has two FindNodeCalls outstanding, so
- * its transmit queue is idle when the lookup completes).  Everything else is OVS_ENOTSUP, on the host,
+ * its transmit queue is idle when the lookup completes), and on a Pastry context under iterative routing
+ * (OVS_HAS_DHT_PASTRY, with the Pastry block below).  Everything else is OVS_ENOTSUP, on the host,
  * before anything is staged; DESIGN.md lists each refusal. */
 #define OVS_HAS_DHT 1
 typedef struct ovs_dht_params {
@@ -1305,10 +1306,19 @@ ovs_status  ovs_broose_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const u
  * below).  Refused with OVS_ENOTSUP: routeMsgAcks, numberOfNeighbors != 0, bitsPerDigit outside 1..4,
  * odd numberOfLeaves or above 32, the full-recursive and source-routing types.  Of the application tiers Scribe runs on a
  * Pastry context built by ovs_pastry_load (ovs_scribe_*, OVS_HAS_SCRIBE_PASTRY) and the overlay broadcast on one
- * from either loader (ovs_pastry_broadcast_batch, OVS_HAS_PASTRY_BROADCAST).  Everything else on one --
- * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, every other application tier -- is refused with
- * OVS_ENOTSUP (ovs_chord_broadcast_batch, which names its overlay: OVS_ESTATE). */
+ * from either loader (ovs_pastry_broadcast_batch, OVS_HAS_PASTRY_BROADCAST), and so does the DHT tier under
+ * iterative routing (ovs_dht_*, ovs_dhttest_stats_batch; OVS_HAS_DHT_PASTRY below).  Everything else on one --
+ * ovs_route_batch, ovs_lookup_batch, ovs_find_node_batch, ovs_rpc_batch, the replica-team DHTs -- is refused
+ * with OVS_ENOTSUP (ovs_chord_broadcast_batch, which names its overlay: OVS_ESTATE).
+ *
+ * DHT on Pastry (additive to ABI 12; test OVS_HAS_DHT_PASTRY): the DHT calls of OVS_HAS_DHT on a Pastry
+ * context from either loader with params.routingType = 0, unchanged in arguments and records.  The lookup
+ * phase is ovs_pastry_lookup_batch's LookupCall with num_siblings = dht.numReplica (same hop count, latency
+ * and status; its conditions, OVS_ENOTSUP naming the key otherwise); routeMsgAcks does not enter.
+ * getMaxNumSiblings() is numberOfLeaves / 2: a larger dht.numReplica is OVS_ENOTSUP.  On a network with
+ * fewer nodes than numReplica the operation uses the siblings there are. */
 #define OVS_HAS_PASTRY 1
+#define OVS_HAS_DHT_PASTRY 1
 enum { OVS_OVERLAY_PASTRY = 6 };
 typedef struct ovs_pastry_params {
     int32_t bitsPerDigit;       /* **.pastry.bitsPerDigit = 4 (default.ini:226) */

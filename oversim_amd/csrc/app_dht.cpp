@@ -1,6 +1,7 @@
 // app_dht.cpp -- the DHT tier (DHT.cc) and DHTTestApp's statistics.  The lookup phase is the LookupCall
-// seam (lookup_check / lookup_device) on this call's staged copies; dht.hip adds the replica phase and
-// owns the storage.  Every refusal happens before anything is staged.
+// seam (lookup_check / lookup_device; on a Pastry context pastry_lookup_check / pastry_lookup_device) on this
+// call's staged copies; dht.hip adds the replica phase and owns the storage.  Every refusal happens before
+// anything is staged.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -23,7 +24,10 @@ ovs_status dht_check(ovs_ctx* c, const ovs_dht_params* dp, hipStream_t s)
     if (c->overlay == OVS_OVERLAY_BROOSE)
         return fail(c, OVS_ENOTSUP, "DHT on Broose: LookupCalls (ovs_lookup_batch) are not implemented for Broose");
     const bool chord = c->overlay == OVS_OVERLAY_CHORD;
-    if (chord ? (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n)) : (c->kad.lo != 0 || c->kad.hi != c->n))
+    // a Pastry context is never a shard; its LookupCall is pastry_lookup_check / pastry_lookup_device
+    const bool pastry = c->overlay == OVS_OVERLAY_PASTRY;
+    if (!pastry &&
+        (chord ? (c->ideal && (c->shard_lo != 0 || c->shard_hi != c->n)) : (c->kad.lo != 0 || c->kad.hi != c->n)))
         return fail(c, OVS_ENOTSUP, "DHT on a shard context: the storage and the LookupCall need the whole network on one device");
     if (c->P.routingType != 0)
         return fail(c, OVS_ENOTSUP, "DHT with a recursive or exhaustive routingType: the lookup's messages are not the "
@@ -41,11 +45,13 @@ ovs_status dht_check(ovs_ctx* c, const ovs_dht_params* dp, hipStream_t s)
     if (!(dp->ratioIdentical > 0 && dp->ratioIdentical <= 1))
         return fail(c, OVS_ENOTSUP, "dht.ratioIdentical outside (0, 1]: a get could wait for ever with no hash chosen");
     // DHT.cc:84-87: "numReplica bigger than what this overlay can handle"
-    if (dp->numReplica > (chord ? c->P.successorListSize : c->P.s))
+    // ... on Pastry numberOfLeaves / 2 (BasePastry.cc:1090-1093)
+    if (dp->numReplica > (pastry ? c->pastry.sh.L / 2 : chord ? c->P.successorListSize : c->P.s))
         return fail(c, OVS_ENOTSUP, "dht.numReplica > getMaxNumSiblings()");
     if (!c->dht.slots) return fail(c, OVS_ESTATE, "no DHT store: ovs_dht_store_create first");
     int32_t ns;
-    return lookup_check(c, c->P, dp->numReplica, s, &ns);
+    // a DHT operation sends FindNodeCalls and direct RPCs, no route message: routeMsgAcks does not enter
+    return pastry ? pastry_lookup_check(c, c->P, dp->numReplica, &ns) : lookup_check(c, c->P, dp->numReplica, s, &ns);
 }
 
 DhtConsts dht_consts(const ovs_ctx* c, const ovs_dht_params* dp)
@@ -169,7 +175,8 @@ ovs_status dht_batch(ovs_ctx* c, const ovs_dht_params* dp, const ovs_key160* key
     ovs_lookup_out* dlook = reinterpret_cast<ovs_lookup_out*>(buf.data());
     uint32_t* dsib = reinterpret_cast<uint32_t*>(buf.data() + o_sib);
     // DHT.cc:504-516, 523-535: LookupCall{key, numSiblings = numReplica}, an internal RPC
-    st = lookup_device(c, c->P, C.R, dk, ds, n, reinterpret_cast<ovs_route_out*>(dlook), dsib, s);
+    st = c->overlay == OVS_OVERLAY_PASTRY ? pastry_lookup_device(c, c->P, C.R, dk, ds, n, dlook, dsib, s)
+                                          : lookup_device(c, c->P, C.R, dk, ds, n, reinterpret_cast<ovs_route_out*>(dlook), dsib, s);
     if (st != OVS_OK) return st;
     hipError_t e;
     DhtHeader h{};

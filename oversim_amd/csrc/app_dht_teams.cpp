@@ -26,6 +26,9 @@ ovs_status team_check(ovs_ctx* c, const ovs_dht_params* dp, const ovs_dht_team_p
     if (c->overlay == OVS_OVERLAY_KADEMLIA)
         return fail(c, OVS_ENOTSUP, "replica teams on Kademlia: the replay needs a route chain that does not depend on "
                                     "time, and a Kademlia lookup's next FindNodeCalls depend on which responses came first");
+    if (c->overlay == OVS_OVERLAY_PASTRY)
+        return fail(c, OVS_ENOTSUP, "replica teams on Pastry: the replay takes its chains from a one-way route that no "
+                                    "timeout ends, and a Pastry lookup's chain branches to the start vector on timeouts");
     if (c->overlay == OVS_OVERLAY_CHORD && !c->ideal)
         return fail(c, OVS_ENOTSUP, "replica teams on explicit Chord tables: the replay takes its chains from the "
                                     "no-timeout route of a converged ring");

@@ -195,6 +195,18 @@ ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, co
 ovs_status lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_siblings, hipStream_t s, int32_t* ns);
 ovs_status lookup_device(ovs_ctx* c, const ovs_params& P, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
                          ovs_route_out* dout, uint32_t* dsib, hipStream_t s);
+// The iterative LookupCall on a Pastry context (ovs_pastry.cpp), for ovs_pastry_lookup_batch and the DHT tier.
+// pastry_lookup_check: pastry_iterative_refusal, check_common, num_siblings (< 0: numberOfLeaves / 2; 0 and more
+// than that refused) into *ns, the device selected.  route: the one-way message's refusals too (routeMsgAcks,
+// numSiblings); name: the entry point a num_siblings = 0 refusal names.
+ovs_status pastry_lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_siblings, int32_t* ns, bool route = false,
+                               const char* name = "ovs_pastry_lookup_batch");
+// pastry_lookup_device: n > 0 lookups on device pointers, queued on s, after pastry_lookup_check and
+// check_sources; dsib has ns entries per lookup.  The visited lists come from the cached kvis buffer unless the
+// caller brings dhop (n * hopCountMax); drout instead of dlook: the one-way route (ns = 1); drpc: RPC counts.
+ovs_status pastry_lookup_device(ovs_ctx* c, const ovs_params& P, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
+                                ovs_lookup_out* dlook, uint32_t* dsib, hipStream_t s, ovs_route_out* drout = nullptr,
+                                uint32_t* dhop = nullptr, uint32_t* drpc = nullptr);
 
 // ---- read-backs ----
 // the control words of a frontier loop (queue length, error bits, ...), read after the launches queued on s

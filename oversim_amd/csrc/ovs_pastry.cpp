@@ -1,8 +1,8 @@
 // ovs_pastry.cpp -- the Pastry entry points of the C ABI (include/ovs_kbr.h): the loaders, the export, the
 // findNode batch, the semi-recursive route (pastry_route_device: the public call's and Scribe's publish leg) and
-// the iterative lookup (pastry_iter_call: the LookupCall batch and the one-way route under iterative routing).
-// The generic calls and the other application tiers refuse a Pastry context through refuse_dedicated
-// (ovs_route.cpp); Scribe runs on one (app_scribe.cpp).
+// the iterative lookup (pastry_lookup_check / pastry_lookup_device: the LookupCall batch, the one-way route under
+// iterative routing and the DHT tier's lookup phase).  The generic calls refuse a Pastry context through
+// refuse_dedicated (ovs_route.cpp); Scribe, the overlay broadcast and the DHT tier run on one (app_*.cpp).
 #include <string>
 #include <vector>
 
@@ -39,7 +39,8 @@ DelayConsts pastry_iter_delay_consts(const ovs_params& P)
     return d;
 }
 
-// the two iterative entry points: lout + siblings (a LookupCall) or rout (the one-way route)
+// the two iterative entry points: lout + siblings (a LookupCall) or rout (the one-way route), on the two halves
+// the DHT tier uses as well
 ovs_status pastry_iter_call(ovs_ctx* c, const char* name, bool route, const ovs_key160* keys, const uint32_t* src, uint64_t n,
                             int32_t ns, ovs_route_out* rout, ovs_lookup_out* lout, uint32_t* siblings, uint32_t* hop_seq, uint32_t* rpcs,
                             uint32_t flags, void* stream)
@@ -47,16 +48,8 @@ ovs_status pastry_iter_call(ovs_ctx* c, const char* name, bool route, const ovs_
     if (!c || (n && (!keys || !src || (route ? !rout : !lout || !siblings)))) return OVS_EINVAL;
     if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
     const ovs_params& P = c->P;
-    if (const char* why = pastry_iterative_refusal(P, c->pastry_bp, route)) return fail(c, OVS_ENOTSUP, why);
-    ovs_status st = check_common(c, P);
+    ovs_status st = pastry_lookup_check(c, P, ns, &ns, route, name);
     if (st != OVS_OK) return st;
-    // getMaxNumSiblings (BasePastry.cc:1090-1093); lookupRpc turns a negative count into it (BaseOverlay.cc:1940-1944)
-    const int maxsib = c->pastry.sh.L / 2;
-    if (ns < 0) ns = maxsib;
-    if (ns == 0)
-        return fail(c, OVS_ENOTSUP, std::string(name) + ": exact-key lookups (num_siblings = 0) are not implemented on Pastry");
-    if (ns > maxsib) return fail(c, OVS_EINVAL, "numSiblings too big! (num_siblings must be 1..numberOfLeaves/2 or -1)");
-    HIPCHK(c, hipSetDevice(c->device));
     const bool dev = flags & OVS_DEVICE_PTRS;
     hipStream_t s = dev ? (hipStream_t)stream : c->stream;
     if (n == 0) return OVS_OK;
@@ -71,19 +64,43 @@ ovs_status pastry_iter_call(ovs_ctx* c, const char* name, bool route, const ovs_
     uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
     uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
     if (!F.ok()) return frame_fail(c, F);
-    CachedBuf::Lease vis;
-    if ((st = visited_lists(c, &dhop, n, H, s, &vis)) != OVS_OK) return st;
-    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-    const hipError_t e = pastry_iter(c->pastry, pastry_iter_delay_consts(P), P.hopCountMax, ns, dk, ds, n, dro, dlo, dsib, dhop, drpc,
-                                     c->num_cu, s, dyn.get());
-    vis.release();
-    if (e != hipSuccess) return hip_fail(c, e, "pastry iterative lookup kernel");
+    if ((st = pastry_lookup_device(c, P, ns, dk, ds, n, dlo, dsib, s, dro, dhop, drpc)) != OVS_OK) return st;
     return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
 }
 
 }  // namespace
 
 namespace ovs {
+
+ovs_status pastry_lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_siblings, int32_t* ns, bool route, const char* name)
+{
+    if (const char* why = pastry_iterative_refusal(P, c->pastry_bp, route)) return fail(c, OVS_ENOTSUP, why);
+    const ovs_status st = check_common(c, P);
+    if (st != OVS_OK) return st;
+    // getMaxNumSiblings (BasePastry.cc:1090-1093); lookupRpc turns a negative count into it (BaseOverlay.cc:1940-1944)
+    const int maxsib = c->pastry.sh.L / 2;
+    if (num_siblings < 0) num_siblings = maxsib;
+    if (num_siblings == 0)
+        return fail(c, OVS_ENOTSUP, std::string(name) + ": exact-key lookups (num_siblings = 0) are not implemented on Pastry");
+    if (num_siblings > maxsib) return fail(c, OVS_EINVAL, "numSiblings too big! (num_siblings must be 1..numberOfLeaves/2 or -1)");
+    HIPCHK(c, hipSetDevice(c->device));
+    *ns = num_siblings;
+    return OVS_OK;
+}
+
+ovs_status pastry_lookup_device(ovs_ctx* c, const ovs_params& P, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
+                                ovs_lookup_out* dlook, uint32_t* dsib, hipStream_t s, ovs_route_out* drout, uint32_t* dhop,
+                                uint32_t* drpc)
+{
+    CachedBuf::Lease vis;
+    const ovs_status st = visited_lists(c, &dhop, n, (uint64_t)P.hopCountMax, s, &vis);
+    if (st != OVS_OK) return st;
+    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+    const hipError_t e = pastry_iter(c->pastry, pastry_iter_delay_consts(P), P.hopCountMax, ns, dk, ds, n, drout, dlook, dsib, dhop, drpc,
+                                     c->num_cu, s, dyn.get());
+    vis.release();
+    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry iterative lookup kernel");
+}
 
 ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, CallFrame&, const K160* dk, const uint32_t* ds, uint64_t n,
                                ovs_route_out* dout, uint32_t* dhop, hipStream_t s)
