@@ -371,7 +371,9 @@ __device__ __forceinline__ PStep pastry_send_to_key(const PView& V, uint32_t cur
 {
     PStep st;
     st.next = NONE;
-    if (a.broken) st.status = OVS_LOOKUP_BROKEN;
+    // findNode throws "numRedundantNodes or numSiblings too big!" above getMaxNumRedundantNodes() = numberOfLeaves
+    // (BasePastry.cc:1095-1098, 1105-1110)
+    if (a.broken || nred > V.sh.L) st.status = OVS_LOOKUP_BROKEN;
     else if (!a.sibvec && a.next == NONE && nred <= 1) st.status = OVS_LOOKUP_NO_NEXT;   // "FindNode() returned NULL" (1449)
     else if (hops >= hcm) st.status = OVS_LOOKUP_HOPMAX;                                  // 1464-1489
     else {

@@ -70,9 +70,10 @@ def replay(M, b):
     return r
 
 
-def model(n, b=4, L=16, rnd=1, R=4, G=4, tmo=1.5, auth=False, ratio=0.5, measured=False):
-    """A fresh DhtModel on pastry_net(n, b, L, rnd), fed by the Pastry LookupCall (measured: through real queues)."""
-    pn = pastry_net(n, b, L, rnd)
+def model(n, b=4, L=16, rnd=1, R=4, G=4, tmo=1.5, auth=False, ratio=0.5, measured=False, ids=None, xy=None):
+    """A fresh DhtModel on pastry_net(n, b, L, rnd), or on the n sorted ids and coordinates given, fed by the Pastry
+    LookupCall (measured: through real queues)."""
+    pn = pastry_net(n, b, L, rnd) if ids is None else RP.PastryNet(ids, xy, b, L, rnd=bool(rnd))
     look = (DP.pastry_measured_lookup if measured else DP.pastry_lookup)(pn, R, rpc_to=tmo, auth=auth)
     return D.DhtModel(pn.xy, look, bool(rnd), R, G, ratio, rpc_udp_timeout=tmo, auth=auth)
 

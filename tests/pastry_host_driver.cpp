@@ -124,6 +124,33 @@ int main()
             }
         }
     }
+    // key arithmetic for the test to redo in Python ints: borrows and carries through equal or saturated middle
+    // words, shared prefixes that end in every word, every digit of every digit size (b = 3: the digits that
+    // straddle bits 31/32, 63/64, 95/96, 127/128)
+    const uint32_t F = 0xFFFFFFFFu;
+    const uint32_t ks[][5] = {{0, 0, 0, 0, 0}, {1, 0, 0, 0, 0}, {F, F, 0, 0, 0}, {0, 0, 1, 0, 0}, {F, F, F, F, 0}, {0, 0, 0, 0, 1},
+                              {F, F, F, F, F}, {0xA5A5A5A5u, 0xA5A5A5A5u, 0xA5A5A5A5u, 0xA5A5A5A5u, 0xA5A5A5A5u},
+                              {0x12345678u, 0xABCDEF89u, 0x0D159E00u, 0x2000u, 0x048D159Cu}, {0x9ABCDEF0u, 0xABCDEF89u, 0x0D159E00u, 0x2000u, 0x048D159Cu},
+                              {5, 0, 0x80000000u, 0, 0}, {9, 0, 0x80000000u, 0, 0x80000000u}, {0x80000001u, 3, 0, 0x80000000u, 1}};
+    const int nk = (int)(sizeof ks / sizeof ks[0]);
+    auto hex = [](const K160& k) { std::printf(" %08x%08x%08x%08x%08x", k.w[4], k.w[3], k.w[2], k.w[1], k.w[0]); };
+    for (int i = 0; i < nk; ++i) {
+        K160 a;
+        std::memcpy(a.w, ks[i], sizeof a.w);
+        for (int b = 1; b <= 4; ++b) {
+            std::printf("digits %d", b);
+            hex(a);
+            for (int n = 0; n < 160 / b; ++n) std::printf(" %u", p_digit(a, n, b));
+            std::printf("\n");
+        }
+        for (int j = 0; j < nk; ++j) {
+            K160 c;
+            std::memcpy(c.w, ks[j], sizeof c.w);
+            std::printf("arith");
+            hex(a); hex(c); hex(k_sub(a, c)); hex(k_add(a, c)); hex(p_ring_dist(a, c));
+            std::printf(" %d %d\n", i == j ? 160 : p_spl_bits(a, c), k_lt(a, c) ? 1 : 0);
+        }
+    }
     if (fails) return 1;
     std::printf("ok\n");
     return 0;

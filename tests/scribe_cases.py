@@ -11,12 +11,14 @@ def key_words(x: int) -> np.ndarray:
     return np.array([(x >> (32 * i)) & 0xFFFFFFFF for i in range(5)], dtype=np.uint32)
 
 
-def scenario(n: int, seed: int = 7):
+def scenario(n: int, seed: int = 7, ids=None, xy=None):
     """A ring of n nodes with four groups: 0 has a node ID as its key and its root among the members; 1 has a
     key between two nodes and a root that is no member; 2 has no members; 3's key is 1's plus one, so both
-    share root and forwarders.  Duplicate pairs are included.  Returns (ids, xy, group_keys, members)."""
-    net = W.population(n, 100 + n)
-    ids, xy = net.ids, net.xy
+    share root and forwarders.  Duplicate pairs are included.  ids, xy: the n sorted ids and coordinates to use
+    instead of a random population.  Returns (ids, xy, group_keys, members)."""
+    if ids is None:
+        net = W.population(n, 100 + n)
+        ids, xy = net.ids, net.xy
     rng = np.random.default_rng(seed + n)
     r0 = 3 % n
     k1 = (to_int(ids[(n // 2) % n]) + 12345) % (1 << 160)

@@ -15,6 +15,7 @@ import dht_pastry_cases as X
 import refmodel_dht as D
 from oversim_amd import (DHT_GET_DTYPE, DHT_PUT_DTYPE, DhtParams, DhtTeamParams, KbrEngine, KbrError, Params,
                          PastryParams)
+from oversim_amd.kbr import Network
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -23,8 +24,8 @@ CAP = 1 << 14
 SMALLEST = 2                       # ovs_pastry_load: "Pastry needs at least 2 nodes"
 
 
-def load(engine, n, b=4, L=16, rnd=1, tmo=1.5, auth=0, acks=0, **pk):
-    net = X.population(n)
+def load(engine, n, b=4, L=16, rnd=1, tmo=1.5, auth=0, acks=0, ids=None, xy=None, **pk):
+    net = X.population(n) if ids is None else Network(ids=ids, xy=xy)
     engine.set_params(Params.pastry().replace(routingType=0, simtimeRound=rnd, rpcUdpTimeout=tmo, measureAuthBlock=auth, **pk))
     engine.pastry_load(net.ids, net.xy, PastryParams.default(routeMsgAcks=acks, bitsPerDigit=b, numberOfLeaves=L))
     return net

@@ -12,6 +12,7 @@ import pytest
 from oversim_amd import KbrEngine, KbrError, Params, PastryParams, workload as W
 from oversim_amd.kbr import key_from_int
 import refmodel_pastry as RP
+from pastry_cases import assert_routes as _assert_routes, find_node_want as _find_node_want
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -32,34 +33,11 @@ def _load(engine, n, seed=81, b=4, L=16, opt=0, reg=1, **pk):
     return net, m
 
 
-def _assert_routes(got, want, what=""):
-    for f in FIELDS:
-        bad = np.flatnonzero(got[f] != want[f])
-        assert len(bad) == 0, (what, f, bad[:5], got[f][bad[:5]], want[f][bad[:5]])
-    H = min(got["hop_seq"].shape[1], want["hop_seq"].shape[1])
-    assert np.array_equal(got["hop_seq"][:, :H], want["hop_seq"][:, :H]), what
-    assert np.all(got["hop_seq"][:, H:] == NONE) and np.all(want["hop_seq"][:, H:] == NONE), what
-
-
 def _batch(net, nq, seed):
     rng = np.random.default_rng(seed)
     keys = W.random_keys(nq, rng)
     keys[::4] = net.ids[rng.integers(0, len(net.ids), len(keys[::4]))]
     return keys, rng.integers(0, len(net.ids), nq).astype(np.uint32)
-
-
-def _find_node_want(m, node, keys, nr, ns, cols):
-    out = np.full((len(node), cols), NONE, dtype=np.uint32)
-    cnt, sib, st = (np.zeros(len(node), dtype=np.uint8) for _ in range(3))
-    for i, (v, k) in enumerate(zip(node, keys)):
-        try:
-            res, info = m.nodes[int(v)].find_node(RP.to_int(k), nr, ns)
-        except RP.PastryError:
-            st[i] = 2
-            continue
-        out[i, :len(res)] = res
-        cnt[i], sib[i], st[i] = len(res), info["sib"], 1 if info["err"] else 0
-    return out, cnt, sib, st
 
 
 @pytest.mark.parametrize("n", [2, 3, 9, 17, 40, 1000])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oversim_amd import workload as W
+import pastry_cases as PC
 import refmodel_pastry as RP
 from refmodel_pastry import PastryNet, key_dist, ring_dist, shared_prefix_length
 
@@ -38,33 +39,81 @@ def test_leaf_rule_is_the_merge_replay(n, L):
         assert m.rule_leaves(0)[L // 2 - 1] == n - 1 and m.rule_leaves(0)[L // 2] == 1
 
 
-@pytest.mark.parametrize("b", [1, 2, 4])
+def _scan_rule(m, v):
+    """Node v's rows by the rule and the two rows after them against a scan of all ids; rows past the key's last
+    whole digit (bitsPerDigit = 3 leaves bit 0 over) do not exist."""
+    ids, b = m.ids, m.b
+    me = ids[v]
+    rows = m.rule_rows(v)
+    assert any(x is not None for x in rows[-1])
+    for r in range(min(len(rows) + 2, 160 // b)):
+        p = 160 - (r + 1) * b
+        for c in range(1 << b):
+            cls = [i for i, k in enumerate(ids)
+                   if i != v and shared_prefix_length(k, me, b) >= r and ((k >> p) & ((1 << b) - 1)) == c
+                   and (me >> (p + b)) == (k >> (p + b))]
+            if ((me >> p) & ((1 << b) - 1)) == c:
+                want = None
+            elif not cls:
+                want = None
+            else:
+                t = (me & ~(((1 << b) - 1) << p)) | (c << p)
+                up = [i for i in cls if ids[i] >= t]
+                want = min(up, key=lambda i: ids[i]) if up else min(cls, key=lambda i: ids[i])
+            got = rows[r][c] if r < len(rows) else m.rule_entry(v, r, c)
+            assert got == want, (v, r, c)
+            if want is not None:
+                assert shared_prefix_length(ids[want], me, b) == r
+
+
+@pytest.mark.parametrize("b", [1, 2, 3, 4])
 def test_table_rule_is_a_brute_force_scan(b):
     net = W.population(300, 6)
     m = PastryNet(net.ids, net.xy, b, 16, nodes=[])
-    ids = m.ids
     for v in random.Random(b).sample(range(300), 12):
-        me = ids[v]
-        rows = m.rule_rows(v)
-        assert any(x is not None for x in rows[-1])
-        for r in range(len(rows) + 2):
-            p = 160 - (r + 1) * b
-            for c in range(1 << b):
-                cls = [i for i, k in enumerate(ids)
-                       if i != v and shared_prefix_length(k, me, b) >= r and ((k >> p) & ((1 << b) - 1)) == c
-                       and (me >> (p + b)) == (k >> (p + b))]
-                if ((me >> p) & ((1 << b) - 1)) == c:
-                    want = None
-                elif not cls:
-                    want = None
-                else:
-                    t = (me & ~(((1 << b) - 1) << p)) | (c << p)
-                    up = [i for i in cls if ids[i] >= t]
-                    want = min(up, key=lambda i: ids[i]) if up else min(cls, key=lambda i: ids[i])
-                got = rows[r][c] if r < len(rows) else m.rule_entry(v, r, c)
-                assert got == want, (v, r, c)
-                if want is not None:
-                    assert shared_prefix_length(ids[want], me, b) == r
+        _scan_rule(m, v)
+
+
+@pytest.mark.parametrize("b", [1, 2, 3, 4])
+@pytest.mark.parametrize("name", PC.FAMILIES)
+def test_table_rule_on_the_deep_families(name, b):
+    """Every node of tests/pastry_cases.py's families: tables of 33 to 160 rows, classes that start at index 0 or
+    end at n, the class whose upper bound is 2^160, digits that straddle a word."""
+    ids, _, xy = PC.family(name, b)
+    m = PastryNet(ids, xy, b, 16, nodes=[])
+    for v in range(m.n):
+        _scan_rule(m, v)
+    rows = m.num_rows()
+    if name == "low_word":
+        assert 128 // b < rows <= 160 // b
+        assert all(all(x is None for x in row) for row in m.rule_rows(0)[:128 // b])
+    if name == "ladder":
+        base = ids.index(int.from_bytes(b"\xA5" * 20, "big"))
+        assert rows == m.num_rows(base) == 160 // b
+        assert all(sum(x is not None for x in row) == b for row in m.rule_rows(base))     # one a bit of the digit
+    if name == "wrap":
+        top = m.rule_rows(0)[0]                                  # node 0's first row: the class that ends at 2^160
+        assert top[(1 << b) - 1] is not None and ids[top[(1 << b) - 1]] >> (160 - b) == (1 << b) - 1
+
+
+@pytest.mark.parametrize("b,L", PC.SHAPES)
+@pytest.mark.parametrize("name", PC.FAMILIES)
+def test_deep_family_routes_end_at_the_owner(name, b, L):
+    """RP.routes over the families' probe keys in the three forms of the next hop: a delivered route ends at
+    PastryNet.owner(key).  The census is what tests/test_gpu_pastry_deep.py relies on."""
+    keys, src = PC.probes(name, b)
+    for opt, reg in PC.FORMS:
+        m = PC.model(name, b, L, opt, reg)
+        for rnr in (1, 3):
+            want = PC.model_routes(name, b, L, opt, reg, rnr)
+            ok = want["status"] == RP.OK
+            for i in np.flatnonzero(ok):
+                assert int(want["responsible"][i]) in m.owner(RP.to_int(keys[i])), (opt, reg, rnr, i)
+                assert (want["hops"][i] == 0) == (want["responsible"][i] == src[i])
+            if L == 2 and rnr == 3:
+                assert (want["status"] == RP.BROKEN).all()       # numRedundantNodes > numberOfLeaves: findNode throws
+            else:
+                assert ok.mean() >= 0.95, (opt, reg, rnr, PC.status_census(want))
 
 
 def test_key_arithmetic():
@@ -156,3 +205,18 @@ def test_host_driver_under_sanitizers(tmp_path):
         assert [None if x == "-1" else int(x) for x in vals.split()] == m.rule_leaves(v), line
         seen += 1
     assert seen > 20
+    # key160.hpp / pastry_host.hpp arithmetic against Python ints: k_sub, k_add, p_ring_dist, p_spl_bits, k_lt on
+    # pairs whose borrows and carries run through equal or saturated words, and p_digit at every position
+    pairs = digits = 0
+    for line in r.stdout.splitlines():
+        f = line.split()
+        if f and f[0] == "arith":
+            a, c, sub, add, dist = (int(x, 16) for x in f[1:6])
+            assert sub == (a - c) % RP.M and add == (a + c) % RP.M and dist == ring_dist(a, c) == key_dist(a, c), line
+            assert int(f[6]) == shared_prefix_length(a, c) and int(f[7]) == int(a < c), line
+            pairs += 1
+        elif f and f[0] == "digits":
+            b, a = int(f[1]), int(f[2], 16)
+            assert [int(x) for x in f[3:]] == [(a >> (160 - (n + 1) * b)) & ((1 << b) - 1) for n in range(160 // b)], line
+            digits += 1
+    assert pairs == 13 * 13 and digits == 13 * 4
