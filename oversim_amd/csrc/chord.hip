@@ -138,19 +138,36 @@ __global__ void k_chord_win(const KeyRec* __restrict__ recs, uint32_t n, uint32_
         o[j] = make_uint4((uint32_t)g[2 * j], (uint32_t)(g[2 * j] >> 32), (uint32_t)g[2 * j + 1], (uint32_t)(g[2 * j + 1] >> 32));
 }
 
-// complete every finger entry from its finger's NodeRec (rerun when the NodeRecs change)
-__global__ void k_chord_entries(const NodeRec* __restrict__ nodes, FingerEnt* __restrict__ ents, uint64_t total)
+// complete every finger entry from its finger's NodeRec (rerun when the NodeRecs change); a window of
+// 8 successors goes in coarsely too (window codes, engine.hpp), from the distances k_chord_win writes
+__global__ void k_chord_entries(const KeyRec* __restrict__ recs, uint32_t n, int ns, const NodeRec* __restrict__ nodes,
+                                FingerEnt* __restrict__ ents, uint64_t total)
 {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
     const uint32_t f = ents[e].idx;
     const uint4* q = reinterpret_cast<const uint4*>(nodes + f);
     const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
+    const uint64_t gS0 = (uint64_t)c.z | ((uint64_t)c.w << 32), gSL = (uint64_t)d.x | ((uint64_t)d.y << 32);
+    uint64_t g[6] = {};
+    if (ns == 8 && gSL) {
+        K160 C;
+        C.w[0] = a.x; C.w[1] = a.y; C.w[2] = a.z; C.w[3] = a.w; C.w[4] = b.x;
+        #pragma unroll
+        for (int j = 1; j <= 6; ++j) {
+            uint32_t sj = f + (uint32_t)j + 1;
+            while (sj >= n) sj -= n;
+            g[j - 1] = top64(k_sub(key_of(load_rec(recs, sj)), C));
+        }
+    }
+    uint64_t gS0c;
+    uint32_t wc;
+    finger_pack(gS0, gSL, g, ns == 8, &gS0c, &wc);
     uint4* o = reinterpret_cast<uint4*>(ents + e);
     o[0] = a;                                     // key
     o[1] = make_uint4(b.x, f, b.z, b.w);          // key[4], idx, x
-    o[2] = c;                                     // y, gS0
-    o[3] = make_uint4(d.x, d.y, b.y, 0u);         // gSL, the finger's row offset
+    o[2] = make_uint4(c.x, c.y, (uint32_t)gS0c, (uint32_t)(gS0c >> 32));   // y, gS0 (48 bits), codes 1, 2
+    o[3] = make_uint4(d.x, d.y, b.y, wc);         // gSL, the finger's row offset, codes 3..6
 }
 
 // resolved getFinger(pos) for every position (test export)
@@ -452,6 +469,10 @@ struct Hdr {
     K160 k;
     uint32_t row;
     double x, y;
+    // gS0 is the line's raw word: a NodeRec's full gS0, a finger entry's gS0c (engine.hpp) whose low
+    // FINGER_GS0_DROP bits are window codes.  Every use drops those bits (cmp_gap<FINGER_GS0_DROP>, the
+    // ilo guard); finger_codes() takes the codes from the same word.  Masking at unpack and carrying
+    // the codes apart would add a live register to the 95 of the 96 the DEF instantiation has
     uint64_t gS0, gSL;
 };
 
@@ -469,10 +490,12 @@ __device__ __forceinline__ int msb64(uint64_t x) { return 63 - __clzll((long lon
 __device__ __forceinline__ uint64_t u64(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
 
 // sign of (D - gap) where gap = key(recs[g]) - C and gt = top64(gap): decided on the top
-// 64 bits, exact on a tie
+// 64 bits -- on the top 64 - DROP where gt carries no more (a finger entry's gS0) --, exact on a tie
+template <int DROP = 0>
 __device__ __forceinline__ int cmp_gap(const ChordView& V, const K160& D, uint64_t gt, const K160& C, uint32_t g)
 {
-    const uint64_t Dt = top64(D);
+    const uint64_t Dt = top64(D) >> DROP;
+    gt >>= DROP;
     if (Dt != gt) return Dt < gt ? -1 : 1;
     const K160 G = k_sub(key_of(load_rec(V.recs, g)), C);
     return k_lt(D, G) ? -1 : (k_eq(D, G) ? 0 : 1);
@@ -993,18 +1016,35 @@ __global__ __launch_bounds__(256, SHARD ? OVS_K1_SHARD_WAVES : OVS_K1_WAVES) voi
                     C = A.k; row = A.row; gSL = A.gSL; gTx = false;
                     if (!SHARD) Dt = top64(D);
                     const uint32_t s0 = ring_next(cur, 1, V.n);
-                    if (cmp_gap(V, D, A.gS0, C, s0) <= 0) {
+                    // (A.gS0 of either line on the 48 bits a finger entry carries: its low 16 are codes there)
+                    if (cmp_gap<FINGER_GS0_DROP>(V, D, A.gS0, C, s0) <= 0) {
                         nx2 = s0; nx2_sib = true;                      // K in (C, succ0] (Chord.cc:583-590)
                     } else {
-                        ilo = A.gS0 ? 97 + msb64(A.gS0) : k_msb(k_sub(key_of(load_rec(V.recs, s0)), C)) + 1;
+                        ilo = (A.gS0 >> FINGER_GS0_DROP) ? 97 + msb64(A.gS0) : k_msb(k_sub(key_of(load_rec(V.recs, s0)), C)) + 1;
                         esl = gSL ? 97 + msb64(gSL) : 96;
                         const uint32_t sl = ring_next(cur, (uint32_t)ns, V.n);
                         const int c = cmp_gap(V, D, gSL, C, sl);
                         if (c < 0) {
+                            // K inside the window.  A responder reached through a finger entry (ph is still
+                            // PH_PROBE) brought its window codes: the farthest successor short of K is
+                            // decided from them here, unless one ties with K's (engine.hpp).  g_0 < D < g_7
+                            // are the two compares above, so K is no successor's key and the next hop
+                            // is that successor (the WIN phase's !tIsK case) -- its line is requested in
+                            // this iteration instead of the WinRec.  (The shard step leaves the window to
+                            // PH_WIN: with the codes another rank would decide a remote responder's hop)
+                            bool coded = false;
+                            if (!SHARD && ph == PH_PROBE) {
+                                const uint64_t codes = finger_codes(A.gS0, L3.w);
+                                if (finger_has_codes(codes)) {
+                                    bool tie;
+                                    const int tj = finger_win_scan(codes, (uint32_t)(top64(D) >> max(esl - 104, 0)), &tie);
+                                    if (!tie) { nx2 = ring_next(cur, (uint32_t)tj + 1, V.n); coded = true; }
+                                }
+                            }
                             if (SHARD && remote) {
                                 redo_hand();                       // the window exists on the owner only
-                            } else {
-                                lp = reinterpret_cast<const uint4*>(V.win + (cur - V.lo));   // K inside the window
+                            } else if (!coded) {
+                                lp = reinterpret_cast<const uint4*>(V.win + (cur - V.lo));
                                 ph = PH_WIN;
                             }
                         } else {
@@ -1234,7 +1274,7 @@ hipError_t launch_chord_nodes(const KeyRec* recs, const double2* xy, uint32_t n,
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_chord_nodes, dim3(nblk(n, 256)), dim3(256), 0, s, recs, xy, n, ns, nodes);
     if (hi > lo) hipLaunchKernelGGL(k_chord_win, dim3(nblk(hi - lo, 256)), dim3(256), 0, s, recs, n, lo, hi - lo, ns, win);
-    if (nfing) hipLaunchKernelGGL(k_chord_entries, dim3(nblk(nfing, 256)), dim3(256), 0, s, nodes, fingers, nfing);
+    if (nfing) hipLaunchKernelGGL(k_chord_entries, dim3(nblk(nfing, 256)), dim3(256), 0, s, recs, n, ns, nodes, fingers, nfing);
     return hipGetLastError();
 }
 
@@ -1246,10 +1286,11 @@ hipError_t launch_chord_top(const KeyRec* recs, uint32_t n, int L, FingerEnt* ft
     return hipGetLastError();
 }
 
-hipError_t launch_chord_entries(const NodeRec* nodes, FingerEnt* ents, uint64_t total, hipStream_t s)
+hipError_t launch_chord_entries(const KeyRec* recs, uint32_t n, int ns, const NodeRec* nodes, FingerEnt* ents,
+                                uint64_t total, hipStream_t s)
 {
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_chord_entries, dim3(nblk(total, 256)), dim3(256), 0, s, nodes, ents, total);
+    hipLaunchKernelGGL(k_chord_entries, dim3(nblk(total, 256)), dim3(256), 0, s, recs, n, ns, nodes, ents, total);
     return hipGetLastError();
 }
 

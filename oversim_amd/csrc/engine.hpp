@@ -2,6 +2,7 @@
 // MI355X lookup-routing engine (internal; the public boundary is include/ovs_kbr.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "key160.hpp"
@@ -141,12 +142,14 @@ struct alignas(64) FingerEnt {
     uint32_t w[5];   // finger key
     uint32_t idx;    // finger node index
     double x, y;     // finger coordinates
-    uint64_t gS0;    // the finger's own window distances (its NodeRec fields)
-    uint64_t gSL;
+    uint64_t gS0c;   // bits 63..16: the top 48 bits of the finger's gS0; bits 15..0: window codes 1, 2
+    uint64_t gSL;    // the finger's gSL (its NodeRec field)
     uint32_t row;    // the finger's own row offset
-    uint32_t pad;
+    uint32_t wc;     // window codes 3..6, one byte each (code 3 lowest)
 };
 static_assert(sizeof(FingerEnt) == 64, "FingerEnt is one 64 B line");
+static_assert(offsetof(FingerEnt, gS0c) == offsetof(NodeRec, gS0) && offsetof(FingerEnt, gSL) == offsetof(NodeRec, gSL),
+              "a lane unpacks either line the same way");
 
 // WinRec: per node of the arc, top64(succ_j - v) for j = 0..7 (unused slots all-ones);
 // read only when K falls inside the successor window.
@@ -155,6 +158,73 @@ struct alignas(64) WinRec {
 };
 
 __device__ __host__ __forceinline__ uint64_t top64(const K160& a) { return (uint64_t)a.w[3] | ((uint64_t)a.w[4] << 32); }
+
+// ---- the window fields of a FingerEnt.  Besides gSL an entry carries a coarse copy of its finger's
+// successor window, so that a lookup arriving through the entry with K inside that window picks the
+// successor without reading the finger's WinRec:
+//  * gS0 narrowed to its top 48 bits (bits 159..112 of succ0 - v).  A compare against it is decided
+//    when the top 48 bits differ, as a top64 compare is when the 64 differ; equal bits take the
+//    exact keys in recs[] either way.
+//  * six window codes, code_j = g_j >> sh for the interior successors j = 1..6 of a window of 8
+//    (g_j = top64(succ_j - v), what the WinRec holds), sh = finger_code_shift(gSL).  g_j <= gSL, so a
+//    code fits in 8 bits, and codes never decrease in j.  code_j != Dt >> sh decides g_j against Dt;
+//    equal codes decide nothing, and the lookup reads the WinRec as before.
+//  * "no codes" -- the window has not 8 successors, or gSL == 0 -- is code 1 = 0xFF above code 6 = 0.
+constexpr int FINGER_GS0_DROP = 16;                    // low bits of gS0 a finger entry does not carry
+constexpr uint64_t FINGER_NO_CODES = 0x0000000000FFull;
+
+__device__ __host__ __forceinline__ int finger_code_shift(uint64_t gSL)
+{
+    const int m = gSL ? 63 - __builtin_clzll(gSL) : 0;
+    return m > 7 ? m - 7 : 0;
+}
+
+// the six codes of an entry, code j in byte j - 1
+__device__ __host__ __forceinline__ uint64_t finger_codes(uint64_t gS0c, uint32_t wc)
+{
+    return (gS0c & 0xFFFFull) | ((uint64_t)wc << 16);
+}
+
+__device__ __host__ __forceinline__ bool finger_has_codes(uint64_t codes)
+{
+    return (uint32_t)(codes & 0xFF) <= (uint32_t)(codes >> 40);
+}
+
+// the finger's gS0 as far as the entry carries it (low FINGER_GS0_DROP bits zero)
+__device__ __host__ __forceinline__ uint64_t finger_gs0(uint64_t gS0c) { return gS0c & ~0xFFFFull; }
+
+// an entry's gS0c and wc from its finger's gS0, gSL and interior window distances g[0..5] = g_1..g_6
+// (coded == false: a window of another size, no codes)
+__device__ __host__ __forceinline__ void finger_pack(uint64_t gS0, uint64_t gSL, const uint64_t (&g)[6], bool coded,
+                                                     uint64_t* gS0c, uint32_t* wc)
+{
+    uint64_t codes = FINGER_NO_CODES;
+    if (coded && gSL) {
+        const int sh = finger_code_shift(gSL);
+        codes = 0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) codes |= ((g[j] >> sh) & 0xFF) << (8 * j);
+    }
+    *gS0c = finger_gs0(gS0) | (codes & 0xFFFF);
+    *wc = (uint32_t)(codes >> 16);
+}
+
+// the farthest successor j of a window of 8 with g_j < Dt, from the codes and cD = Dt >> sh, given that
+// g_0 < Dt < g_7 is known: the number of interior codes below cD.  *tie: an interior code equals cD
+// (the result is then not decided)
+__device__ __host__ __forceinline__ int finger_win_scan(uint64_t codes, uint32_t cD, bool* tie)
+{
+    int tj = 0;
+    bool eq = false;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const uint32_t cj = (uint32_t)(codes >> (8 * j)) & 0xFF;
+        tj += cj < cD ? 1 : 0;
+        eq |= cj == cD;
+    }
+    *tie = eq;
+    return tj;
+}
 
 __device__ __forceinline__ double dbl(uint32_t lo, uint32_t hi) { return __hiloint2double((int)hi, (int)lo); }
 

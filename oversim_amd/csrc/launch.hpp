@@ -21,7 +21,9 @@ hipError_t launch_chord_nodes(const KeyRec* recs, const double2* xy, uint32_t n,
                               FingerEnt* fingers, uint64_t nfing, WinRec* win, uint32_t lo, uint32_t hi, hipStream_t s);
 // replicated top finger levels of a sharded ring (finger indices; launch_chord_entries completes them)
 hipError_t launch_chord_top(const KeyRec* recs, uint32_t n, int L, FingerEnt* ftop, hipStream_t s);
-hipError_t launch_chord_entries(const NodeRec* nodes, FingerEnt* ents, uint64_t total, hipStream_t s);
+// (ns: the successor window of the NodeRecs, which the entries copy coarsely)
+hipError_t launch_chord_entries(const KeyRec* recs, uint32_t n, int ns, const NodeRec* nodes, FingerEnt* ents,
+                                uint64_t total, hipStream_t s);
 hipError_t launch_chord_export(const KeyRec* recs, const FingerEnt* fingers, uint32_t n, uint32_t* out,
                                hipStream_t s);
 // perm != nullptr: qkeys / qsrc are the batch in key order (ksort_launch), perm[q] the caller index of

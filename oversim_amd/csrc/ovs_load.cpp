@@ -37,7 +37,7 @@ ovs_status ensure_nodes(ovs_ctx* c, hipStream_t s)
     HIPCHK(c, launch_chord_nodes(c->recs, c->xy, (uint32_t)c->n, ns, c->nodes, c->fingers, c->nfing, c->win,
                                  (uint32_t)c->shard_lo, (uint32_t)c->shard_hi, s));
     // the replicated top levels carry their fingers' window distances too
-    if (c->ftop) HIPCHK(c, launch_chord_entries(c->nodes, c->ftop, c->n * (uint64_t)c->ftl, s));
+    if (c->ftop) HIPCHK(c, launch_chord_entries(c->recs, (uint32_t)c->n, ns, c->nodes, c->ftop, c->n * (uint64_t)c->ftl, s));
     // the records are built once and then read by kernels on any stream (e.g. one stream per
     // cohort of ovs_shard_step): complete them before any other call can see nodes_ns set
     HIPCHK(c, hipStreamSynchronize(s));

@@ -166,7 +166,7 @@ ovs_status ovs_chord_shard_replicate(ovs_ctx* c, int32_t top_levels)
     HIPCHK(c, hipMalloc(&c->ftop, sizeof(FingerEnt) * tot));
     c->ftl = top_levels;
     HIPCHK(c, launch_chord_top(c->recs, (uint32_t)c->n, top_levels, c->ftop, c->stream));
-    if (c->nodes) HIPCHK(c, launch_chord_entries(c->nodes, c->ftop, tot, c->stream));
+    if (c->nodes) HIPCHK(c, launch_chord_entries(c->recs, (uint32_t)c->n, c->nodes_ns, c->nodes, c->ftop, tot, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return OVS_OK;
 }
