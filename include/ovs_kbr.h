@@ -1326,7 +1326,8 @@ typedef struct ovs_pastry_params {
     int32_t numberOfNeighbors;  /* **.pastry.numberOfNeighbors = 0 (default.ini:228) */
     int32_t optimizeLookup;     /* **.pastry.optimizeLookup = false (default.ini:234) */
     int32_t useRegularNextHop;  /* **.pastry.useRegularNextHop = true (default.ini:236) */
-    int32_t routeMsgAcks;       /* **.pastry.routeMsgAcks = true (default.ini:245): refused at the route; set 0 */
+    int32_t routeMsgAcks;       /* **.pastry.routeMsgAcks = true (default.ini:245): ovs_pastry_acked_route_batch and
+                                   ovs_pastry_rpc_batch run it; the calls without acks refuse it */
 } ovs_pastry_params;
 void        ovs_pastry_params_default(ovs_pastry_params* out);
 /* Reads the **.overlay*.pastry.* keys above from ini text (config_name as for ovs_params_from_ini) into *bp,
@@ -1427,6 +1428,59 @@ ovs_status  ovs_pastry_iterative_route_batch(ovs_ctx* ctx, const ovs_key160* key
 ovs_status  ovs_pastry_broadcast_batch(ovs_ctx* ctx, const uint32_t* initiators, uint64_t nb, int32_t ttl,
                                        int32_t query_bytes, ovs_bcast_node* nodes, ovs_bcast_stats* stats,
                                        uint32_t flags, void* stream);
+
+/* ---- Pastry routes with per-hop acks and the RPC test (additive to ABI 12; test OVS_HAS_PASTRY_ACKS,
+ * OVS_HAS_PASTRY_RPC) ----
+ * The reference ships Pastry with routeMsgAcks = true (default.ini:245): sendRouteMessage wraps every route
+ * message in a NextHopCall (BaseOverlay.cc:1135-1144; NEXTHOPCALL_L = BASECALL_L = 256 bits around the message,
+ * CommonMessages.msg:69-71, 88) and the receiver answers with a NextHopResponse (NEXTHOPRESPONSE_L =
+ * BASERESPONSE_L = 256 bits + AUTHBLOCK_L under measureAuthBlock, CommonMessages.msg:73-76, 89) before it
+ * handles the message (nextHopRpc, BaseOverlay.cc:1971-2000: the response at 1997, the message at 1999).  A
+ * forwarder therefore queues its next NextHopCall behind its own ack (SimpleNodeEntry::calcDelay,
+ * SimpleNodeEntry.cc:164-194), so each forward leaves one ack's serialisation time late; the source's queue is
+ * idle.  That term, the longer message and each hop's ack round trip (sendUdpRpcCall to the response's
+ * arrival, the wait in the sender's own queue included) are exact int64 arithmetic.  Traffic of other lookups
+ * is not carried, as in every batch: each route starts with all transmit queues idle.
+ *
+ * An ack round trip >= rpcUdpTimeout is a timeout (BaseRpc.cc:191-211).  The reference has delivered the first
+ * copy all the same; its sender then runs handleFailedNode and routes the message again (BaseOverlay.cc:
+ * 1697-1757).  A batch holds the tables fixed: the route record is the first copy's delivery, the ack record
+ * names the first hop whose ack timed out, and the repair and the duplicate are the caller's between batches.
+ *
+ * ovs_pastry_acked_route_batch: the KBRTestApp one-way message on a Pastry context from either loader under the
+ * context's routeMsgAcks.  out / hop_seq / keys / src / flags / stream as ovs_pastry_route_batch; ack_out (n
+ * records) may be NULL.  routeMsgAcks = 0: exactly ovs_pastry_route_batch's records and empty ack records
+ * (acks 0, max_ack_rtt_ns -1, timeout_hop 0xFF).  params.routingType = 0 (iterative): the lookup of
+ * ovs_pastry_iterative_route_batch, hop_seq as there; the final sendRouteMessage (BaseOverlay.cc:1254-1257)
+ * goes as one NextHopCall from the source, so only that message's length and one ack change.  A route that
+ * fails part-way (OVS_LOOKUP_HOPMAX, _NO_NEXT, _BROKEN) has sent the NextHopCalls of the hops it took, and its
+ * ack record counts them.
+ *
+ * ovs_pastry_rpc_batch: KBRTestApp's RPC test (kbrRpcTest; ovs_rpc_batch's records and rpcKeyTimeout rule) under
+ * semi-recursive routing and either routeMsgAcks.  The call leg is the route above.  The KbrTestResponse goes
+ * straight back over UDP (BaseOverlay.cc:1340-1341); where the call arrived in a NextHopCall the responder has
+ * just queued that call's ack, and the response leaves behind it; a caller that is its own responder answers
+ * at once.  ovs_kbrtest_rpc_stats_batch and ovs_kbrtest_stats_batch take these records on a Pastry context.
+ *
+ * OVS_ENOTSUP naming the key, on the host before anything is staged: what ovs_pastry_route_batch (or, under
+ * iterative routing, ovs_pastry_iterative_route_batch) refuses apart from routeMsgAcks; the full-recursive and
+ * source-routing types; the RPC test under iterative routing; a testMsgSize with which one NextHopResponse and
+ * one NextHopCall exceed sendQueueLength = 1MB (default.ini:553) in a transmit queue, where the reference
+ * drops.  OVS_ESTATE: another overlay's context or no network.  The existing calls keep their refusals. */
+#define OVS_HAS_PASTRY_ACKS 1
+#define OVS_HAS_PASTRY_RPC 1
+typedef struct ovs_pastry_ack_out {
+    int64_t  max_ack_rtt_ns;  /* the largest ack round trip of the route's NextHopCalls; -1 when none was sent */
+    uint16_t acks;            /* NextHopCalls sent, each acknowledged */
+    uint8_t  timeout_hop;     /* 0-based index of the first NextHopCall whose ack round trip reached rpcUdpTimeout
+                                 (0 = the source's; indices above 254 read 254); 0xFF = none */
+    uint8_t  pad[5];          /* written as 0 */
+} ovs_pastry_ack_out;
+ovs_status  ovs_pastry_acked_route_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n,
+                                         ovs_route_out* out, ovs_pastry_ack_out* ack_out, uint32_t* hop_seq,
+                                         uint32_t flags, void* stream);
+ovs_status  ovs_pastry_rpc_batch(ovs_ctx* ctx, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_rpc_out* out,
+                                 uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_rpc_finish(const ovs_route_out* __restr
             uint32_t rh = 0;
             if (r.responsible != s) {
                 const double2 a = xy[r.responsible], b = xy[s];
-                d = RC.respMsg + coord_ns(a.x, a.y, b.x, b.y, RC.round);
+                d = RC.respQueue + RC.respMsg + coord_ns(a.x, a.y, b.x, b.y, RC.round);
                 rh = 1;
             }
             const int64_t rtt = r.latency_ns + d;

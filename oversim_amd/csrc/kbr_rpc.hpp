@@ -11,6 +11,8 @@ struct RpcConsts {
     int32_t round;       // SimTime(double) rounding rule
     int32_t full;        // full-recursive routing: the response is a second route
     uint32_t nnodes;
+    int64_t respQueue;   // what the responder's transmit queue holds ahead of the response: 0, or on Pastry under
+                         // routeMsgAcks T(L*8/datarate) of the NextHopResponse it has just sent (ovs_pastry_rpc_batch)
 };
 
 // Pass 1 over the call routes: writes out[i]; full-recursive routing: also the return route's inputs

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "kbr_rpc.hpp"
 
 using namespace ovs;
 
@@ -37,6 +38,67 @@ DelayConsts pastry_iter_delay_consts(const ovs_params& P)
     d.bwCall = bw(d.callBytes);
     for (int i = 0; i <= 16; ++i) d.bwResp[i] = bw(d.respBase + d.respPerNode * i);
     return d;
+}
+
+// routes under routeMsgAcks: the constants beside DelayConsts (PastryAckConsts, pastry.hpp)
+PastryAckConsts pastry_ack_consts(const ovs_params& P, const DelayConsts& DC)
+{
+    PastryAckConsts a{};
+    a.bwAck = bw_host(P, (int32_t)pastry_nexthop_ack_bytes(P));
+    a.msgAck = 2 * a.bwAck + DC.access2;
+    a.msgCall = 2 * bw_host(P, (int32_t)pastry_nexthop_call_bytes(P)) + DC.access2;
+    a.timeout = DC.rpcTimeout;
+    return a;
+}
+
+// The one-way message on device pointers under the context's routeMsgAcks and routingType, after
+// pastry_acked_refusal: dack may be nullptr; dhop as the plain calls take it.
+ovs_status pastry_acked_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
+                               ovs_route_out* dout, ovs_pastry_ack_out* dack, uint32_t* dhop, hipStream_t s)
+{
+    const bool acks = c->pastry_bp.routeMsgAcks != 0;
+    hipError_t e = hipSuccess;
+    if (P.routingType == 0) {
+        // the lookup is ovs_pastry_iterative_route_batch's; the final sendRouteMessage goes as one NextHopCall
+        // (BaseOverlay.cc:1254-1257), which changes that message's length and adds its ack
+        DelayConsts DC = pastry_iter_delay_consts(P);
+        const PastryAckConsts AC = pastry_ack_consts(P, DC);
+        if (acks) DC.msgRoute = AC.msgCall;
+        CachedBuf::Lease vis;
+        ovs_status st = visited_lists(c, &dhop, n, (uint64_t)P.hopCountMax, s, &vis);
+        if (st != OVS_OK) return st;
+        const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+        e = pastry_iter(c->pastry, DC, P.hopCountMax, 1, dk, ds, n, dout, nullptr, nullptr, dhop, nullptr, c->num_cu, s, dyn.get());
+        vis.release();
+        if (e != hipSuccess) return hip_fail(c, e, "pastry iterative lookup kernel");
+        if (dack)
+            e = acks ? pastry_iter_acks(dout, ds, c->xy, (uint32_t)c->n, AC, P.simtimeRound, n, dack, s) : pastry_acks_none(n, dack, s);
+        return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry ack record kernel");
+    }
+    if (!acks) {
+        const ovs_status st = pastry_route_device(c, P, F, dk, ds, n, dout, dhop, s);
+        if (st != OVS_OK) return st;
+        if (dack) e = pastry_acks_none(n, dack, s);
+        return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry ack record kernel");
+    }
+    const uint64_t H = (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
+    if (dhop) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
+    const DelayConsts DC = delay_consts(P);
+    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
+    e = pastry_route_acked(c->pastry, DC, pastry_ack_consts(P, DC), P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout, dack, dhop,
+                           c->num_cu, s, dyn.get());
+    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry acked route kernel");
+}
+
+// what both new calls check on the host before anything is staged
+ovs_status pastry_acked_begin(ovs_ctx* c, bool rpc)
+{
+    if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
+    const ovs_status st = check_common(c, c->P);
+    if (st != OVS_OK) return st;
+    if (const char* why = pastry_acked_refusal(c->P, c->pastry_bp, rpc)) return fail(c, OVS_ENOTSUP, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    return OVS_OK;
 }
 
 // the two iterative entry points: lout + siblings (a LookupCall) or rout (the one-way route), on the two halves
@@ -260,6 +322,68 @@ ovs_status ovs_pastry_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint
     uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
     if (!F.ok()) return frame_fail(c, F);
     if ((st = pastry_route_device(c, P, F, dk, ds, n, dout, dhop, s)) != OVS_OK) return st;
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+}
+
+ovs_status ovs_pastry_acked_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_route_out* out,
+                                        ovs_pastry_ack_out* ack_out, uint32_t* hop_seq, uint32_t flags, void* stream)
+{
+    static_assert(sizeof(ovs_pastry_ack_out) == 16, "ovs_pastry_ack_out is 16 B");
+    if (!c || (n && (!keys || !src || !out))) return OVS_EINVAL;
+    ovs_status st = pastry_acked_begin(c, false);
+    if (st != OVS_OK) return st;
+    const ovs_params& P = c->P;
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    if (n == 0) return OVS_OK;
+    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
+    const uint64_t H = P.routingType == 0 ? (uint64_t)P.hopCountMax : (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
+    CallFrame F(dev, s);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_route_out* dout = F.out(out, n);
+    ovs_pastry_ack_out* dack = ack_out ? F.out(ack_out, n) : nullptr;
+    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
+    if (!F.ok()) return frame_fail(c, F);
+    if ((st = pastry_acked_device(c, P, F, dk, ds, n, dout, dack, dhop, s)) != OVS_OK) return st;
+    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+}
+
+// KBRTestApp's RPC test on Pastry (KBRTestApp.cc:172-189, 230-329): the call leg is the route above; the
+// KbrTestResponse goes straight back (BaseOverlay.cc:1340-1341) behind the ack the responder has just sent,
+// which k_rpc_finish adds as RpcConsts::respQueue; its timeout rule is ovs_rpc_batch's.
+ovs_status ovs_pastry_rpc_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_rpc_out* out, uint32_t flags,
+                                void* stream)
+{
+    if (!c || (n && (!keys || !src || !out))) return OVS_EINVAL;
+    ovs_status st = pastry_acked_begin(c, true);
+    if (st != OVS_OK) return st;
+    const ovs_params& P = c->P;
+    if (!(P.rpcKeyTimeout >= 0)) return fail(c, OVS_EINVAL, "rpcKeyTimeout must be >= 0");
+    const bool dev = flags & OVS_DEVICE_PTRS;
+    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
+    if (n == 0) return OVS_OK;
+    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
+    CallFrame F(dev, s);
+    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
+    const uint32_t* ds = F.in(src, n);
+    ovs_rpc_out* dout = F.out(out, n);
+    if (!F.ok()) return frame_fail(c, F);
+    CachedBuf::Lease buf = c->rpcb.acquire(sizeof(ovs_route_out) * n, s);
+    if (!buf) return lease_fail(c, "RPC buffers", buf);
+    ovs_route_out* droute = reinterpret_cast<ovs_route_out*>(buf.data());
+    if ((st = pastry_acked_device(c, P, F, dk, ds, n, droute, nullptr, nullptr, s)) != OVS_OK) return st;
+    const DelayConsts DC = delay_consts(P);
+    RpcConsts RC{};
+    RC.timeout = simtime_host(P.rpcKeyTimeout, P.simtimeRound);
+    RC.respMsg = 2 * bw_host(P, (int32_t)pastry_rpc_response_bytes(P)) + DC.access2;
+    RC.respQueue = c->pastry_bp.routeMsgAcks ? pastry_ack_consts(P, DC).bwAck : 0;
+    RC.round = P.simtimeRound;
+    RC.full = 0;
+    RC.nnodes = (uint32_t)c->n;
+    const hipError_t e = launch_rpc_finish(droute, ds, c->recs, c->xy, RC, n, dout, nullptr, nullptr, c->num_cu, s);
+    if (e != hipSuccess) return hip_fail(c, e, "RPC finish kernel");
+    buf.release();
     return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
 }
 

@@ -5,7 +5,8 @@
 // routing-table slot two bisections over the sorted ids.  pastry_find_node_dev (pastry_dev.hpp) is
 // BasePastry::findNode at one node: the one restatement, called by the findNode batch kernel and by every hop of
 // k_pastry_route, which runs one lane per semi-recursive route message (BaseOverlay::sendToKey's recursive branch,
-// pastry_send_to_key) on the persistent-slice scheduler of persist.hpp.  A hop reads the node's record, its leaf
+// pastry_send_to_key) on the persistent-slice scheduler of persist.hpp; k_pastry_route_acked is the same route
+// under routeMsgAcks, every hop a NextHopCall with its ack.  A hop reads the node's record, its leaf
 // row and the one table slot the key addresses; the table rows are scanned only for the closer-node fallback and
 // when the first candidate of a numRedundantNodes > 1 answer is refused.  k_pastry_iter runs one lane per
 // IterativeLookup (a LookupCall with its sibling vector, or the one-way message under iterative routing) on the
@@ -226,6 +227,129 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
             active = false;
         }
     }
+}
+
+// The route under routeMsgAcks (BaseOverlay.cc:1107-1146): every hop is a NextHopCall around the route message,
+// and its receiver sends the NextHopResponse before it forwards (nextHopRpc, 1971-2000), so a forwarder's
+// transmit queue holds the ack when the next call enters it (SimpleNodeEntry.cc:164-194: tx.finished =
+// max(tx.finished, now) + bits / bandwidth) and the call leaves AC.bwAck late.  The source's queue is idle.  A
+// node met twice has drained its queue long before: two hops lie between, each longer than ack plus call.  The
+// sender of the call that arrives now forwarded iff hops > 1, so the lane carries only the largest ack round
+// trip (sendUdpRpcCall to the response's arrival, the wait in the sender's own queue included) and the first
+// hop whose round trip reached rpcUdpTimeout (a tie is a timeout, BaseRpc.cc:191-211).  The route record is the
+// first copy's delivery; the re-route after a timeout (BaseOverlay.cc:1697-1757) is the caller's between batches.
+// A route that fails part-way has sent, and had acknowledged, the calls of the hops it took.
+__global__ __launch_bounds__(256) void k_pastry_route_acked(PView V, DelayConsts DC, PastryAckConsts AC, int hcm, int nred,
+                                                            const K160* __restrict__ qkeys, const uint32_t* __restrict__ qsrc,
+                                                            uint64_t nq, uint64_t chunk, PersistDyn dy,
+                                                            ovs_route_out* __restrict__ out, ovs_pastry_ack_out* __restrict__ aout,
+                                                            uint32_t* __restrict__ hopseq)
+{
+    PersistFeed<KP_TUNE.dyn_chunk> feed(chunk, dy, nq);
+    const uint64_t H = (uint64_t)max(hcm, 1);
+
+    bool active = false, local = true;
+    uint64_t q = 0;
+    K160 K;
+    K.w[0] = K.w[1] = K.w[2] = K.w[3] = K.w[4] = 0;
+    uint32_t S = 0, cur = 0, last = NONE;
+    double sx = 0, sy = 0;            // the last sender
+    int64_t t = 0, rttmax = -1;
+    int hops = 0;                     // NextHopCalls sent, each acknowledged by the time the lane ends
+    uint32_t tohop = 0xFF;
+    while (true) {
+        if (feed.take(active, dy, nq, q)) {
+            active = true;
+            local = true;
+            K = qkeys[q];
+            S = qsrc[q];
+            cur = S;
+            last = NONE;
+            t = 0; hops = 0;
+            rttmax = -1; tohop = 0xFF;
+        }
+        if (!__any(active)) break;
+        if (!active) continue;
+
+        const PRec Rc = load_prec(V.rec, cur);
+        const PAns a = pastry_find_node_dev(V, cur, Rc, K, 1);
+        uint8_t status = 0xFF;       // 0xFF = still running
+        const bool at_src = local;
+        if (!local) {
+            const int64_t cd = coord_ns(sx, sy, Rc.x, Rc.y, DC.round);
+            const int64_t d = (hops > 1 ? AC.bwAck : 0) + AC.msgCall + cd;      // the call, behind the sender's own ack
+            const int64_t rtt = d + AC.msgAck + cd;                             // the ack leaves an idle queue
+            t += d;
+            rttmax = rtt > rttmax ? rtt : rttmax;
+            if (rtt >= AC.timeout && tohop == 0xFF) tohop = (uint32_t)min(hops - 1, 0xFE);
+        }
+        local = false;
+        sx = Rc.x; sy = Rc.y;
+        if (!at_src && a.closest) status = OVS_LOOKUP_OK;
+        else {
+            const PStep st = pastry_send_to_key(V, cur, Rc, K, a, hops, hcm, nred, last, S);
+            status = st.status;
+            if (status == PSTEP_FORWARD) {
+                if (hopseq) hopseq[q * H + (uint64_t)hops] = st.next;   // hops < hcm here
+                ++hops;
+                last = cur;
+                cur = st.next;
+            }
+        }
+        if (status != 0xFF) {
+            ovs_route_out o;
+            const bool ok = status == OVS_LOOKUP_OK;
+            o.responsible = ok ? cur : NONE;
+            o.hops = (uint16_t)(ok ? hops : 0);
+            o.status = status;
+            o.one_way_hops = (uint8_t)(ok ? hops : 0);
+            o.latency_ns = ok ? t : -1;
+            out[q] = o;
+            if (aout) {
+                ovs_pastry_ack_out ao{};
+                ao.max_ack_rtt_ns = rttmax;
+                ao.acks = (uint16_t)hops;
+                ao.timeout_hop = (uint8_t)tohop;
+                aout[q] = ao;
+            }
+            active = false;
+        }
+    }
+}
+
+// the ack records of routes without acks (routeMsgAcks = false)
+__global__ void k_pastry_acks_none(uint64_t n, ovs_pastry_ack_out* __restrict__ aout)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    ovs_pastry_ack_out ao{};
+    ao.max_ack_rtt_ns = -1;
+    ao.timeout_hop = 0xFF;
+    aout[i] = ao;
+}
+
+// The ack records of one-way messages under iterative routing: the final sendRouteMessage (BaseOverlay.cc:
+// 1254-1257) is one NextHopCall from the source, whose queue the lookup left idle, to getResult()[0]; none where
+// that is the source itself or the lookup failed.
+__global__ void k_pastry_iter_acks(const ovs_route_out* __restrict__ rout, const uint32_t* __restrict__ src,
+                                   const double2* __restrict__ xy, uint32_t nnodes, PastryAckConsts AC, int round, uint64_t n,
+                                   ovs_pastry_ack_out* __restrict__ aout)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ovs_route_out r = rout[i];
+    const uint32_t s = src[i];
+    ovs_pastry_ack_out ao{};
+    ao.max_ack_rtt_ns = -1;
+    ao.timeout_hop = 0xFF;
+    if (r.status == OVS_LOOKUP_OK && r.responsible != s && r.responsible < nnodes && s < nnodes) {
+        const double2 a = xy[s], b = xy[r.responsible];
+        const int64_t rtt = AC.msgCall + AC.msgAck + 2 * coord_ns(a.x, a.y, b.x, b.y, round);
+        ao.max_ack_rtt_ns = rtt;
+        ao.acks = 1;
+        if (rtt >= AC.timeout) ao.timeout_hop = 0;
+    }
+    aout[i] = ao;
 }
 
 // ---------------------------------------------------------------------------
@@ -518,6 +642,34 @@ hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCou
     const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
     hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, recNumRedundantNodes, keys,
                        src, nq, pl.chunk, dy, out, hopseq);
+    return hipGetLastError();
+}
+
+hipError_t pastry_route_acked(const PastryTables& t, const DelayConsts& DC, const PastryAckConsts& AC, int hopCountMax,
+                              int recNumRedundantNodes, const K160* keys, const uint32_t* src, uint64_t nq, ovs_route_out* out,
+                              ovs_pastry_ack_out* ack_out, uint32_t* hopseq, int num_cu, hipStream_t st, unsigned long long* dyn)
+{
+    if (nq == 0) return hipSuccess;
+    using K = PersistKernel<k_pastry_route_acked>;
+    const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
+    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
+    hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, AC, hopCountMax, recNumRedundantNodes,
+                       keys, src, nq, pl.chunk, dy, out, ack_out, hopseq);
+    return hipGetLastError();
+}
+
+hipError_t pastry_acks_none(uint64_t nq, ovs_pastry_ack_out* ack_out, hipStream_t st)
+{
+    if (nq == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pastry_acks_none, dim3(nblk(nq, 256)), dim3(256), 0, st, nq, ack_out);
+    return hipGetLastError();
+}
+
+hipError_t pastry_iter_acks(const ovs_route_out* rout, const uint32_t* src, const double2* xy, uint32_t n, const PastryAckConsts& AC,
+                            int round, uint64_t nq, ovs_pastry_ack_out* ack_out, hipStream_t st)
+{
+    if (nq == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pastry_iter_acks, dim3(nblk(nq, 256)), dim3(256), 0, st, rout, src, xy, n, AC, round, nq, ack_out);
     return hipGetLastError();
 }
 

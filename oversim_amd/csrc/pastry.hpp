@@ -31,6 +31,16 @@ struct PastryTables {
     PastryShape sh{};
 };
 
+// Per-launch constants of routes under routeMsgAcks (host: pastry_ack_consts, ovs_pastry.cpp), beside DelayConsts.
+// NextHopCall = BASECALL_L 256 bits around the route message, NextHopResponse = BASERESPONSE_L 256 bits + AUTHBLOCK_L
+// (CommonMessages.msg:69-73, 88-89), each with the 28 B UDP/IP header.
+struct PastryAckConsts {
+    int64_t msgCall;     // 2*T(L*8/datarate) + 2*T(accessDelay) of the NextHopCall
+    int64_t bwAck;       // T(L*8/datarate) of the NextHopResponse: what a forwarder's queue holds ahead of its call
+    int64_t msgAck;      // 2*bwAck + 2*T(accessDelay): the ack's way back
+    int64_t timeout;     // T(rpcUdpTimeout): an ack round trip >= timeout is a timeout
+};
+
 void pastry_free(PastryTables& t);
 // the converged tables by the rule; n - 1 >= numberOfLeaves (smaller networks: the host replays
 // the leaf sets and calls pastry_build_explicit with dtab = nullptr)
@@ -49,6 +59,16 @@ hipError_t pastry_find_node(const PastryTables& t, const uint32_t* node, const K
 hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCountMax, int recNumRedundantNodes, const K160* keys,
                         const uint32_t* src, uint64_t nq, ovs_route_out* out, uint32_t* hopseq, int num_cu, hipStream_t st,
                         unsigned long long* dyn = nullptr);
+// the same routes under routeMsgAcks (k_pastry_route_acked); ack_out may be nullptr
+hipError_t pastry_route_acked(const PastryTables& t, const DelayConsts& DC, const PastryAckConsts& AC, int hopCountMax,
+                              int recNumRedundantNodes, const K160* keys, const uint32_t* src, uint64_t nq, ovs_route_out* out,
+                              ovs_pastry_ack_out* ack_out, uint32_t* hopseq, int num_cu, hipStream_t st,
+                              unsigned long long* dyn = nullptr);
+// ack records of routes that sent no NextHopCall (routeMsgAcks = false)
+hipError_t pastry_acks_none(uint64_t nq, ovs_pastry_ack_out* ack_out, hipStream_t st);
+// ack records of pastry_iter's one-way routes: one NextHopCall src -> rout.responsible where the two differ
+hipError_t pastry_iter_acks(const ovs_route_out* rout, const uint32_t* src, const double2* xy, uint32_t n, const PastryAckConsts& AC,
+                            int round, uint64_t nq, ovs_pastry_ack_out* ack_out, hipStream_t st);
 // batched iterative lookups (k_pastry_iter): LookupCalls with numSiblings 1..numberOfLeaves/2 into lout and
 // siblings (nq * numSiblings, may be nullptr), or one-way routes (numSiblings 1) into rout -- one of the two.
 // hopseq (nq * hopCountMax, hopCountMax >= 1) is required: it is the visited list; rpcs may be nullptr.  DC

@@ -80,6 +80,44 @@ inline const char* pastry_iterative_refusal(const ovs_params& P, const ovs_pastr
     return pastry_shape_refusal(bp);
 }
 
+// ---- routes under routeMsgAcks (ovs_pastry_acked_route_batch, ovs_pastry_rpc_batch) -----------------------------
+// Wire lengths in bytes, the 28 B UDP/IP header counted once.  NEXTHOPCALL_L = BASECALL_L = BASERPC_L = TYPE_L 8 +
+// NONCE_L 32 + NODEHANDLE_L 208 + TIER_L 8 = 256 bits (CommonMessages.msg:30, 34, 42, 52, 69-71, 88) around the
+// route message (BaseOverlay.cc:1135-1144): BASEROUTE_L 424 bits + BASEAPPDATA_L 40 bits + the payload.
+// NEXTHOPRESPONSE_L = BASERESPONSE_L = BASERPC_L + AUTHBLOCK_L (800 bits under measureAuthBlock) with no NCS
+// info (CommonMessages.msg:57, 73-76, 89).
+inline int64_t pastry_nexthop_call_bytes(const ovs_params& P) { return 32 + 58 + (int64_t)P.testMsgSize + 28; }
+inline int64_t pastry_nexthop_ack_bytes(const ovs_params& P) { return 32 + (P.measureAuthBlock ? 100 : 0) + 28; }
+// the direct KbrTestResponse: payload + BASEAPPDATA_L 40 bits (BaseOverlay.cc:1340-1341, CommonMessages.msg:68)
+inline int64_t pastry_rpc_response_bytes(const ovs_params& P) { return (int64_t)P.testMsgSize + 5 + 28; }
+// SimpleUnderlayNetwork.underlayConfigurator.sendQueueLength = 1MB (default.ini:553), read as 10^6 B
+constexpr int64_t PASTRY_SEND_QUEUE_BYTES = 1000000;
+
+// What ovs_pastry_acked_route_batch (rpc false) and ovs_pastry_rpc_batch (rpc true) refuse before they look at
+// the batch: what pastry_route_refusal / pastry_iterative_refusal refuse apart from routeMsgAcks, the routing
+// types without an acked form, and a transmit queue that one ack plus the packet behind it overruns
+// (SimpleNodeEntry.cc:168-181: the reference drops the second packet there).
+inline const char* pastry_acked_refusal(const ovs_params& P, const ovs_pastry_params& bp, bool rpc)
+{
+    ovs_pastry_params plain = bp;
+    plain.routeMsgAcks = 0;
+    if (P.routingType == 0 && !rpc) {
+        if (const char* why = pastry_iterative_refusal(P, plain, true)) return why;
+    } else {
+        if (P.routingType == 0 || P.routingType == 3)
+            return "Pastry: the RPC test is implemented for routingType = semi-recursive (the iterative lookup test is "
+                   "not part of it)";
+        if (const char* why = pastry_route_refusal(P, plain)) return why;
+    }
+    if (P.testMsgSize < 0) return "Pastry: testMsgSize must be >= 0";
+    if (bp.routeMsgAcks)
+        // the KbrTestResponse behind a responder's ack is shorter than the call
+        if (pastry_nexthop_ack_bytes(P) + pastry_nexthop_call_bytes(P) > PASTRY_SEND_QUEUE_BYTES)
+            return "Pastry: a NextHopResponse and the NextHopCall behind it exceed sendQueueLength = 1MB in a forwarder's "
+                   "transmit queue (testMsgSize); the reference drops there and drops are not modelled";
+    return nullptr;
+}
+
 // KeyRingMetric::distance (Comparator.h:121-131) = PastryStateObject::keyDist (PastryStateObject.cc:107-132)
 OVS_HD K160 p_ring_dist(const K160& x, const K160& y)
 {

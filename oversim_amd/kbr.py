@@ -156,6 +156,9 @@ RPC_OUT_DTYPE = np.dtype([("responder", "<u4"), ("hop_count", "<u2"), ("call_hop
                           ("call_latency_ns", "<i8")])
 assert RPC_OUT_DTYPE.itemsize == 32
 RPC_ANSWERED, RPC_TIMEOUT = 0, 1
+PASTRY_ACK_OUT_DTYPE = np.dtype([("max_ack_rtt_ns", "<i8"), ("acks", "<u2"), ("timeout_hop", "u1"), ("pad", "u1", 5)])
+assert PASTRY_ACK_OUT_DTYPE.itemsize == 16
+PASTRY_NO_TIMEOUT_HOP = 0xFF
 DHT_OP_DTYPE = np.dtype([("t0_ns", "<i8"), ("token", "<u8"), ("kind", "<u4"), ("id", "<u4"), ("vlen", "<u4"),
                          ("ttl", "<i4")])
 assert DHT_OP_DTYPE.itemsize == 32
@@ -246,8 +249,8 @@ class PastryParams(C.Structure):
 
     @classmethod
     def default(cls, **kw) -> "PastryParams":
-        """default.ini's values; routeMsgAcks = true among them is refused at the route, so callers pass
-        routeMsgAcks=0."""
+        """default.ini's values.  routeMsgAcks = true among them runs through pastry_acked_lookup and pastry_rpc; the
+        calls that send no acks (pastry_lookup, pastry_iterative_lookup, Scribe) take routeMsgAcks=0."""
         p = cls()
         lib().ovs_pastry_params_default(C.byref(p))
         for k, v in kw.items():
@@ -518,6 +521,8 @@ def lib() -> C.CDLL:
         "ovs_pastry_route_batch": ([vp, vp, vp, u64, vp, vp, u32, vp], C.c_int),
         "ovs_pastry_lookup_batch": ([vp, vp, vp, u64, i32, vp, vp, vp, vp, u32, vp], C.c_int),
         "ovs_pastry_iterative_route_batch": ([vp, vp, vp, u64, vp, vp, u32, vp], C.c_int),
+        "ovs_pastry_acked_route_batch": ([vp, vp, vp, u64, vp, vp, vp, u32, vp], C.c_int),
+        "ovs_pastry_rpc_batch": ([vp, vp, vp, u64, vp, u32, vp], C.c_int),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)
@@ -996,6 +1001,54 @@ class KbrEngine:
                                                            C.c_void_p(out_ptr), None, DEVICE_PTRS,
                                                            C.c_void_p(stream) if stream else None),
                   "ovs_pastry_iterative_route_batch")
+
+    def pastry_acked_lookup(self, keys, src, record_hops: bool = False, ack_records: bool = True) -> dict:
+        """Batched KBRTestApp one-way routes on a Pastry context under its routeMsgAcks
+        (ovs_pastry_acked_route_batch): semi-recursive, or with params.routingType = 0 the iterative lookup whose
+        final message goes as one NextHopCall.  Returns the route fields as lookup() and, per route, acks (the
+        NextHopCalls sent), max_ack_rtt_ns (-1 without one) and timeout_hop (the first hop whose ack round trip
+        reached rpcUdpTimeout, 0xFF = none); ack_records=False passes no ack buffer."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
+        ack = np.empty(n, dtype=PASTRY_ACK_OUT_DTYPE) if ack_records else None
+        hop = np.empty((n, max(self.get_params().hopCountMax, 1)), dtype=np.uint32) if record_hops else None
+        self._chk(self._L.ovs_pastry_acked_route_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), _ptr(ack), _ptr(hop), 0,
+                                                       None), "ovs_pastry_acked_route_batch")
+        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
+        if ack is not None:
+            res.update({f: ack[f].copy() for f in PASTRY_ACK_OUT_DTYPE.names})
+        if hop is not None:
+            res["hop_seq"] = hop
+        return res
+
+    def pastry_acked_lookup_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, ack_out_ptr: int | None = None,
+                                   stream: int | None = None):
+        """Device-resident batch (async on `stream`): out n ovs_route_out, ack_out n ovs_pastry_ack_out or None."""
+        self._chk(self._L.ovs_pastry_acked_route_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n,
+                                                       C.c_void_p(out_ptr), C.c_void_p(ack_out_ptr) if ack_out_ptr else None,
+                                                       None, DEVICE_PTRS, C.c_void_p(stream) if stream else None),
+                  "ovs_pastry_acked_route_batch")
+
+    def pastry_rpc(self, keys, src) -> dict:
+        """Batched routed KbrTestCall round trips on a Pastry context (ovs_pastry_rpc_batch; KBRTestApp with
+        kbrRpcTest, semi-recursive routing, either routeMsgAcks).  Returns the ovs_rpc_out fields as rpcCall()."""
+        keys = keys_array(keys)
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        n = len(keys)
+        if len(src) != n:
+            raise ValueError("keys and src differ in length")
+        out = np.empty(n, dtype=RPC_OUT_DTYPE)
+        self._chk(self._L.ovs_pastry_rpc_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), 0, None), "ovs_pastry_rpc_batch")
+        return {f: out[f].copy() for f in RPC_OUT_DTYPE.names}
+
+    def pastry_rpc_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
+        """Device-resident RPC batch (async on `stream`): out n ovs_rpc_out."""
+        self._chk(self._L.ovs_pastry_rpc_batch(self._h, C.c_void_p(keys_ptr), C.c_void_p(src_ptr), n, C.c_void_p(out_ptr),
+                                               DEVICE_PTRS, C.c_void_p(stream) if stream else None), "ovs_pastry_rpc_batch")
 
     def epichord_load(self, ids, xy, succ, nsucc, pred, npred, lists_full, cache_off, cache_node, cache_last_ns,
                       cache_ttl_ns):
