@@ -294,7 +294,7 @@ ovs_status ovs_scribe_multicast_batch(ovs_ctx* c, const uint32_t* msg_group, con
     // the publish is routed under this call's message length: a copy of the parameters, the context's stay
     ovs_params PR = c->P;
     PR.testMsgSize = call_bytes;
-    st = c->overlay == OVS_OVERLAY_PASTRY ? pastry_route_device(c, PR, F, keys, ds, nm, route, nullptr, s)
+    st = c->overlay == OVS_OVERLAY_PASTRY ? pastry_route_device(c, PR, keys, ds, nm, route, nullptr, s)
                                           : route_device(c, PR, F, keys, ds, nm, route, nullptr, nullptr, s);
     if (st != OVS_OK) return st;
     HIPCHK(c, launch_scribe_publish(SF, SC, c->xy, route, dg, ds, df, nm, dout, queue, s));

@@ -561,10 +561,9 @@ hipError_t broose_route(const BrooseTables& t, const DelayConsts& DC, int hopCou
     // the hop list holds hopCountMax responders and is the visitOnlyOnce list: no limit, no list
     if (!hopseq || hopCountMax < 1) return hipErrorInvalidValue;
     using K = PersistKernel<k_broose_route>;
-    const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, K4_TUNE);
-    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
-    hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, keys, src, right, nq,
-                       pl.chunk, dy, out, hopseq, rpcs);
+    const PersistLaunch pl = persist_launch<K::fn>(nq, num_cu, dyn, K4_TUNE);
+    hipLaunchKernelGGL(K::fn, dim3(pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, keys, src, right, nq, pl.chunk,
+                       pl.dy, out, hopseq, rpcs);
     return hipGetLastError();
 }
 

@@ -187,9 +187,11 @@ ovs_status route_check(ovs_ctx* c, const ovs_params& P, hipStream_t s);
 ovs_status route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
                         ovs_route_out* dout, uint32_t* dhop, uint32_t* drpc, hipStream_t s);
 // route_device's counterpart on a Pastry context (ovs_pastry.cpp): n > 0 semi-recursive routes on device
-// pointers, queued on s, after check_common, pastry_route_refusal and check_sources
-ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
-                               ovs_route_out* dout, uint32_t* dhop, hipStream_t s);
+// pointers, queued on s, after check_common, pastry_route_refusal (pastry_acked_refusal) and check_sources.
+// AC: the routes run under routeMsgAcks with these constants; dack: ack records (empty ones without AC) or nullptr
+ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, const K160* dk, const uint32_t* ds, uint64_t n, ovs_route_out* dout,
+                               uint32_t* dhop, hipStream_t s, const PastryAckConsts* AC = nullptr,
+                               ovs_pastry_ack_out* dack = nullptr);
 // The same for LookupCalls.  lookup_check resolves num_siblings (< 0: the overlay's maximum) into *ns;
 // dsib has max(ns, 1) entries per lookup.
 ovs_status lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_siblings, hipStream_t s, int32_t* ns);
@@ -203,10 +205,11 @@ ovs_status pastry_lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_sibl
                                const char* name = "ovs_pastry_lookup_batch");
 // pastry_lookup_device: n > 0 lookups on device pointers, queued on s, after pastry_lookup_check and
 // check_sources; dsib has ns entries per lookup.  The visited lists come from the cached kvis buffer unless the
-// caller brings dhop (n * hopCountMax); drout instead of dlook: the one-way route (ns = 1); drpc: RPC counts.
+// caller brings dhop (n * hopCountMax); drout instead of dlook: the one-way route (ns = 1); drpc: RPC counts;
+// DC: the delay constants where they differ from the lookup's own (the acked route's final message).
 ovs_status pastry_lookup_device(ovs_ctx* c, const ovs_params& P, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
                                 ovs_lookup_out* dlook, uint32_t* dsib, hipStream_t s, ovs_route_out* drout = nullptr,
-                                uint32_t* dhop = nullptr, uint32_t* drpc = nullptr);
+                                uint32_t* dhop = nullptr, uint32_t* drpc = nullptr, const DelayConsts* DC = nullptr);
 
 // ---- read-backs ----
 // the control words of a frontier loop (queue length, error bits, ...), read after the launches queued on s

@@ -645,10 +645,9 @@ hipError_t koorde_route(const KoordeTables& t, const KeyRec* recs, const double2
     // the chosen instantiation's occupancy-sized grid: static slices, with the dynamic tail when dyn is given
     auto launch = [&](auto k) {
         using K = decltype(k);
-        const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, K3_TUNE);
-        const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
-        hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, kv, xy, DC, hopCountMax, keys, src, nq,
-                           pl.chunk, dy, out, hopseq, rpcs);
+        const PersistLaunch pl = persist_launch<K::fn>(nq, num_cu, dyn, K3_TUNE);
+        hipLaunchKernelGGL(K::fn, dim3(pl.blocks), dim3(256), 0, st, kv, xy, DC, hopCountMax, keys, src, nq, pl.chunk, pl.dy,
+                           out, hopseq, rpcs);
     };
     const bool kr = t.rec != nullptr;
     const bool def = kr && !record && kv.ns == 16 && kv.sb == 4 && kv.useOther == 1 && kv.useSuc == 1 && hopCountMax == 50;

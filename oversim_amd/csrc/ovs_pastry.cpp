@@ -1,8 +1,9 @@
 // ovs_pastry.cpp -- the Pastry entry points of the C ABI (include/ovs_kbr.h): the loaders, the export, the
-// findNode batch, the semi-recursive route (pastry_route_device: the public call's and Scribe's publish leg) and
-// the iterative lookup (pastry_lookup_check / pastry_lookup_device: the LookupCall batch, the one-way route under
-// iterative routing and the DHT tier's lookup phase).  The generic calls refuse a Pastry context through
-// refuse_dedicated (ovs_route.cpp); Scribe, the overlay broadcast and the DHT tier run on one (app_*.cpp).
+// findNode batch, the semi-recursive route (pastry_route_device: the public calls', plain or under routeMsgAcks,
+// and Scribe's publish leg) and the iterative lookup (pastry_lookup_check / pastry_lookup_device: the LookupCall
+// batch, the one-way route under iterative routing and the DHT tier's lookup phase).  The generic calls refuse a
+// Pastry context through refuse_dedicated (ovs_route.cpp); Scribe, the overlay broadcast and the DHT tier run on
+// one (app_*.cpp).
 #include <string>
 #include <vector>
 
@@ -53,53 +54,62 @@ PastryAckConsts pastry_ack_consts(const ovs_params& P, const DelayConsts& DC)
 
 // The one-way message on device pointers under the context's routeMsgAcks and routingType, after
 // pastry_acked_refusal: dack may be nullptr; dhop as the plain calls take it.
-ovs_status pastry_acked_device(ovs_ctx* c, const ovs_params& P, CallFrame& F, const K160* dk, const uint32_t* ds, uint64_t n,
-                               ovs_route_out* dout, ovs_pastry_ack_out* dack, uint32_t* dhop, hipStream_t s)
+ovs_status pastry_acked_device(ovs_ctx* c, const ovs_params& P, const K160* dk, const uint32_t* ds, uint64_t n, ovs_route_out* dout,
+                               ovs_pastry_ack_out* dack, uint32_t* dhop, hipStream_t s)
 {
     const bool acks = c->pastry_bp.routeMsgAcks != 0;
-    hipError_t e = hipSuccess;
-    if (P.routingType == 0) {
-        // the lookup is ovs_pastry_iterative_route_batch's; the final sendRouteMessage goes as one NextHopCall
-        // (BaseOverlay.cc:1254-1257), which changes that message's length and adds its ack
-        DelayConsts DC = pastry_iter_delay_consts(P);
-        const PastryAckConsts AC = pastry_ack_consts(P, DC);
-        if (acks) DC.msgRoute = AC.msgCall;
-        CachedBuf::Lease vis;
-        ovs_status st = visited_lists(c, &dhop, n, (uint64_t)P.hopCountMax, s, &vis);
-        if (st != OVS_OK) return st;
-        const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-        e = pastry_iter(c->pastry, DC, P.hopCountMax, 1, dk, ds, n, dout, nullptr, nullptr, dhop, nullptr, c->num_cu, s, dyn.get());
-        vis.release();
-        if (e != hipSuccess) return hip_fail(c, e, "pastry iterative lookup kernel");
-        if (dack)
-            e = acks ? pastry_iter_acks(dout, ds, c->xy, (uint32_t)c->n, AC, P.simtimeRound, n, dack, s) : pastry_acks_none(n, dack, s);
-        return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry ack record kernel");
+    if (P.routingType != 0) {
+        const PastryAckConsts AC = pastry_ack_consts(P, delay_consts(P));
+        return pastry_route_device(c, P, dk, ds, n, dout, dhop, s, acks ? &AC : nullptr, dack);
     }
-    if (!acks) {
-        const ovs_status st = pastry_route_device(c, P, F, dk, ds, n, dout, dhop, s);
-        if (st != OVS_OK) return st;
-        if (dack) e = pastry_acks_none(n, dack, s);
-        return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry ack record kernel");
-    }
-    const uint64_t H = (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
-    if (dhop) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
-    const DelayConsts DC = delay_consts(P);
-    const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-    e = pastry_route_acked(c->pastry, DC, pastry_ack_consts(P, DC), P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout, dack, dhop,
-                           c->num_cu, s, dyn.get());
-    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry acked route kernel");
+    // the lookup is ovs_pastry_iterative_route_batch's; the final sendRouteMessage goes as one NextHopCall
+    // (BaseOverlay.cc:1254-1257), which changes that message's length and adds its ack
+    DelayConsts DC = pastry_iter_delay_consts(P);
+    const PastryAckConsts AC = pastry_ack_consts(P, DC);
+    if (acks) DC.msgRoute = AC.msgCall;
+    const ovs_status st = pastry_lookup_device(c, P, 1, dk, ds, n, nullptr, nullptr, s, dout, dhop, nullptr, &DC);
+    if (st != OVS_OK || !dack) return st;
+    const hipError_t e =
+        acks ? pastry_iter_acks(dout, ds, c->xy, (uint32_t)c->n, AC, P.simtimeRound, n, dack, s) : pastry_acks_none(n, dack, s);
+    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry ack record kernel");
 }
 
-// what both new calls check on the host before anything is staged
-ovs_status pastry_acked_begin(ovs_ctx* c, bool rpc)
+// The checks of a semi-recursive entry point before anything is staged, in the one order all of them keep: the
+// arguments, the loaded overlay, check_common, the call's own refusal of the parameters (refusal(): its reason
+// or nullptr), the device.
+template <class Refusal>
+ovs_status pastry_begin(ovs_ctx* c, bool args_ok, Refusal refusal)
 {
+    if (!c || !args_ok) return OVS_EINVAL;
     if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
     const ovs_status st = check_common(c, c->P);
     if (st != OVS_OK) return st;
-    if (const char* why = pastry_acked_refusal(c->P, c->pastry_bp, rpc)) return fail(c, OVS_ENOTSUP, why);
+    if (const char* why = refusal()) return fail(c, OVS_ENOTSUP, why);
     HIPCHK(c, hipSetDevice(c->device));
     return OVS_OK;
 }
+
+// What the batch entry points share after their checks: the pointer mode and stream, the empty batch, the sources'
+// range, the frame with the staged keys and sources, and its finish.  A call returns st unless go is set.
+struct PastryBatch {
+    PastryBatch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, uint32_t flags, void* stream)
+        : c(c), dev(flags & OVS_DEVICE_PTRS), s(dev ? (hipStream_t)stream : c->stream), F(dev, s)
+    {
+        if (n == 0 || (st = check_sources(c, src, n, dev)) != OVS_OK) return;
+        dk = F.in(reinterpret_cast<const K160*>(keys), n);
+        ds = F.in(src, n);
+        go = true;
+    }
+    ovs_status finish() { return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F); }
+    ovs_ctx* c;
+    bool dev;
+    hipStream_t s;
+    CallFrame F;
+    const K160* dk = nullptr;      // the staged keys and sources
+    const uint32_t* ds = nullptr;
+    ovs_status st = OVS_OK;        // what the call returns where go is false: an empty batch, a source out of range
+    bool go = false;
+};
 
 // the two iterative entry points: lout + siblings (a LookupCall) or rout (the one-way route), on the two halves
 // the DHT tier uses as well
@@ -112,22 +122,17 @@ ovs_status pastry_iter_call(ovs_ctx* c, const char* name, bool route, const ovs_
     const ovs_params& P = c->P;
     ovs_status st = pastry_lookup_check(c, P, ns, &ns, route, name);
     if (st != OVS_OK) return st;
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    if (n == 0) return OVS_OK;
-    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
-    const uint64_t H = (uint64_t)P.hopCountMax;
-    CallFrame F(dev, s);
-    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
-    const uint32_t* ds = F.in(src, n);
+    PastryBatch B(c, keys, src, n, flags, stream);
+    if (!B.go) return B.st;
+    CallFrame& F = B.F;
     ovs_route_out* dro = rout ? F.out(rout, n) : nullptr;
     ovs_lookup_out* dlo = lout ? F.out(lout, n) : nullptr;
     uint32_t* dsib = siblings ? F.out(siblings, n * (uint64_t)ns) : nullptr;
-    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
+    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * (uint64_t)P.hopCountMax) : nullptr;
     uint32_t* drpc = rpcs ? F.out(rpcs, n) : nullptr;
     if (!F.ok()) return frame_fail(c, F);
-    if ((st = pastry_lookup_device(c, P, ns, dk, ds, n, dlo, dsib, s, dro, dhop, drpc)) != OVS_OK) return st;
-    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+    st = pastry_lookup_device(c, P, ns, B.dk, B.ds, n, dlo, dsib, B.s, dro, dhop, drpc);
+    return st != OVS_OK ? st : B.finish();
 }
 
 }  // namespace
@@ -152,27 +157,29 @@ ovs_status pastry_lookup_check(ovs_ctx* c, const ovs_params& P, int32_t num_sibl
 
 ovs_status pastry_lookup_device(ovs_ctx* c, const ovs_params& P, int32_t ns, const K160* dk, const uint32_t* ds, uint64_t n,
                                 ovs_lookup_out* dlook, uint32_t* dsib, hipStream_t s, ovs_route_out* drout, uint32_t* dhop,
-                                uint32_t* drpc)
+                                uint32_t* drpc, const DelayConsts* DC)
 {
     CachedBuf::Lease vis;
     const ovs_status st = visited_lists(c, &dhop, n, (uint64_t)P.hopCountMax, s, &vis);
     if (st != OVS_OK) return st;
     const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-    const hipError_t e = pastry_iter(c->pastry, pastry_iter_delay_consts(P), P.hopCountMax, ns, dk, ds, n, drout, dlook, dsib, dhop, drpc,
-                                     c->num_cu, s, dyn.get());
+    const hipError_t e = pastry_iter(c->pastry, DC ? *DC : pastry_iter_delay_consts(P), P.hopCountMax, ns, dk, ds, n, drout, dlook, dsib,
+                                     dhop, drpc, c->num_cu, s, dyn.get());
     vis.release();
     return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry iterative lookup kernel");
 }
 
-ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, CallFrame&, const K160* dk, const uint32_t* ds, uint64_t n,
-                               ovs_route_out* dout, uint32_t* dhop, hipStream_t s)
+ovs_status pastry_route_device(ovs_ctx* c, const ovs_params& P, const K160* dk, const uint32_t* ds, uint64_t n, ovs_route_out* dout,
+                               uint32_t* dhop, hipStream_t s, const PastryAckConsts* AC, ovs_pastry_ack_out* dack)
 {
     const uint64_t H = (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
     if (dhop) HIPCHK(c, hipMemsetAsync(dhop, 0xFF, sizeof(uint32_t) * n * H, s));
     const DynSlots::Lease dyn = dyn_acquire(c, n, s);
-    const hipError_t e = pastry_route(c->pastry, delay_consts(P), P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout, dhop,
-                                      c->num_cu, s, dyn.get());
-    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry route kernel");
+    hipError_t e = pastry_route(c->pastry, delay_consts(P), AC, P.hopCountMax, P.recNumRedundantNodes, dk, ds, n, dout,
+                                AC ? dack : nullptr, dhop, c->num_cu, s, dyn.get());
+    if (e != hipSuccess) return hip_fail(c, e, AC ? "pastry acked route kernel" : "pastry route kernel");
+    if (!AC && dack) e = pastry_acks_none(n, dack, s);
+    return e == hipSuccess ? OVS_OK : hip_fail(c, e, "pastry ack record kernel");
 }
 
 }  // namespace ovs
@@ -303,50 +310,34 @@ ovs_status ovs_pastry_find_node_batch(ovs_ctx* c, const uint32_t* node, const ov
 ovs_status ovs_pastry_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_route_out* out,
                                   uint32_t* hop_seq, uint32_t flags, void* stream)
 {
-    if (!c || (n && (!keys || !src || !out))) return OVS_EINVAL;
-    if (c->overlay != OVS_OVERLAY_PASTRY) return fail(c, OVS_ESTATE, "no Pastry network loaded");
-    const ovs_params& P = c->P;
-    ovs_status st = check_common(c, P);
+    ovs_status st = pastry_begin(c, !n || (keys && src && out), [&] { return pastry_route_refusal(c->P, c->pastry_bp); });
     if (st != OVS_OK) return st;
-    if (const char* why = pastry_route_refusal(P, c->pastry_bp)) return fail(c, OVS_ENOTSUP, why);
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    if (n == 0) return OVS_OK;
-    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
-    const uint64_t H = (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
-    CallFrame F(dev, s);
-    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
-    const uint32_t* ds = F.in(src, n);
-    ovs_route_out* dout = F.out(out, n);
-    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
-    if (!F.ok()) return frame_fail(c, F);
-    if ((st = pastry_route_device(c, P, F, dk, ds, n, dout, dhop, s)) != OVS_OK) return st;
-    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+    PastryBatch B(c, keys, src, n, flags, stream);
+    if (!B.go) return B.st;
+    const ovs_params& P = c->P;
+    ovs_route_out* dout = B.F.out(out, n);
+    uint32_t* dhop = hop_seq ? B.F.out(hop_seq, n * (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1)) : nullptr;
+    if (!B.F.ok()) return frame_fail(c, B.F);
+    st = pastry_route_device(c, P, B.dk, B.ds, n, dout, dhop, B.s);
+    return st != OVS_OK ? st : B.finish();
 }
 
 ovs_status ovs_pastry_acked_route_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_route_out* out,
                                         ovs_pastry_ack_out* ack_out, uint32_t* hop_seq, uint32_t flags, void* stream)
 {
     static_assert(sizeof(ovs_pastry_ack_out) == 16, "ovs_pastry_ack_out is 16 B");
-    if (!c || (n && (!keys || !src || !out))) return OVS_EINVAL;
-    ovs_status st = pastry_acked_begin(c, false);
+    ovs_status st = pastry_begin(c, !n || (keys && src && out), [&] { return pastry_acked_refusal(c->P, c->pastry_bp, false); });
     if (st != OVS_OK) return st;
+    PastryBatch B(c, keys, src, n, flags, stream);
+    if (!B.go) return B.st;
     const ovs_params& P = c->P;
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    if (n == 0) return OVS_OK;
-    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
     const uint64_t H = P.routingType == 0 ? (uint64_t)P.hopCountMax : (uint64_t)(P.hopCountMax > 1 ? P.hopCountMax : 1);
-    CallFrame F(dev, s);
-    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
-    const uint32_t* ds = F.in(src, n);
-    ovs_route_out* dout = F.out(out, n);
-    ovs_pastry_ack_out* dack = ack_out ? F.out(ack_out, n) : nullptr;
-    uint32_t* dhop = hop_seq ? F.out(hop_seq, n * H) : nullptr;
-    if (!F.ok()) return frame_fail(c, F);
-    if ((st = pastry_acked_device(c, P, F, dk, ds, n, dout, dack, dhop, s)) != OVS_OK) return st;
-    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+    ovs_route_out* dout = B.F.out(out, n);
+    ovs_pastry_ack_out* dack = ack_out ? B.F.out(ack_out, n) : nullptr;
+    uint32_t* dhop = hop_seq ? B.F.out(hop_seq, n * H) : nullptr;
+    if (!B.F.ok()) return frame_fail(c, B.F);
+    st = pastry_acked_device(c, P, B.dk, B.ds, n, dout, dack, dhop, B.s);
+    return st != OVS_OK ? st : B.finish();
 }
 
 // KBRTestApp's RPC test on Pastry (KBRTestApp.cc:172-189, 230-329): the call leg is the route above; the
@@ -355,36 +346,33 @@ ovs_status ovs_pastry_acked_route_batch(ovs_ctx* c, const ovs_key160* keys, cons
 ovs_status ovs_pastry_rpc_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, ovs_rpc_out* out, uint32_t flags,
                                 void* stream)
 {
-    if (!c || (n && (!keys || !src || !out))) return OVS_EINVAL;
-    ovs_status st = pastry_acked_begin(c, true);
+    ovs_status st = pastry_begin(c, !n || (keys && src && out), [&] { return pastry_acked_refusal(c->P, c->pastry_bp, true); });
     if (st != OVS_OK) return st;
     const ovs_params& P = c->P;
     if (!(P.rpcKeyTimeout >= 0)) return fail(c, OVS_EINVAL, "rpcKeyTimeout must be >= 0");
-    const bool dev = flags & OVS_DEVICE_PTRS;
-    hipStream_t s = dev ? (hipStream_t)stream : c->stream;
-    if (n == 0) return OVS_OK;
-    if ((st = check_sources(c, src, n, dev)) != OVS_OK) return st;
-    CallFrame F(dev, s);
-    const K160* dk = F.in(reinterpret_cast<const K160*>(keys), n);
-    const uint32_t* ds = F.in(src, n);
-    ovs_rpc_out* dout = F.out(out, n);
-    if (!F.ok()) return frame_fail(c, F);
-    CachedBuf::Lease buf = c->rpcb.acquire(sizeof(ovs_route_out) * n, s);
+    PastryBatch B(c, keys, src, n, flags, stream);
+    if (!B.go) return B.st;
+    ovs_rpc_out* dout = B.F.out(out, n);
+    if (!B.F.ok()) return frame_fail(c, B.F);
+    CachedBuf::Lease buf = c->rpcb.acquire(sizeof(ovs_route_out) * n, B.s);
     if (!buf) return lease_fail(c, "RPC buffers", buf);
     ovs_route_out* droute = reinterpret_cast<ovs_route_out*>(buf.data());
-    if ((st = pastry_acked_device(c, P, F, dk, ds, n, droute, nullptr, nullptr, s)) != OVS_OK) return st;
+    // the refusal leaves semi-recursive routing only: the route of pastry_acked_device, and its ack constants once
     const DelayConsts DC = delay_consts(P);
+    const PastryAckConsts AC = pastry_ack_consts(P, DC);
+    const bool acks = c->pastry_bp.routeMsgAcks != 0;
+    if ((st = pastry_route_device(c, P, B.dk, B.ds, n, droute, nullptr, B.s, acks ? &AC : nullptr)) != OVS_OK) return st;
     RpcConsts RC{};
     RC.timeout = simtime_host(P.rpcKeyTimeout, P.simtimeRound);
     RC.respMsg = 2 * bw_host(P, (int32_t)pastry_rpc_response_bytes(P)) + DC.access2;
-    RC.respQueue = c->pastry_bp.routeMsgAcks ? pastry_ack_consts(P, DC).bwAck : 0;
+    RC.respQueue = acks ? AC.bwAck : 0;
     RC.round = P.simtimeRound;
     RC.full = 0;
     RC.nnodes = (uint32_t)c->n;
-    const hipError_t e = launch_rpc_finish(droute, ds, c->recs, c->xy, RC, n, dout, nullptr, nullptr, c->num_cu, s);
+    const hipError_t e = launch_rpc_finish(droute, B.ds, c->recs, c->xy, RC, n, dout, nullptr, nullptr, c->num_cu, B.s);
     if (e != hipSuccess) return hip_fail(c, e, "RPC finish kernel");
     buf.release();
-    return F.finish() == hipSuccess ? OVS_OK : frame_fail(c, F);
+    return B.finish();
 }
 
 ovs_status ovs_pastry_lookup_batch(ovs_ctx* c, const ovs_key160* keys, const uint32_t* src, uint64_t n, int32_t num_siblings,

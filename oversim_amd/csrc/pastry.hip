@@ -4,9 +4,9 @@
 // The build kernels fill the converged tables: a leaf slot is a ring neighbour of the owner, a
 // routing-table slot two bisections over the sorted ids.  pastry_find_node_dev (pastry_dev.hpp) is
 // BasePastry::findNode at one node: the one restatement, called by the findNode batch kernel and by every hop of
-// k_pastry_route, which runs one lane per semi-recursive route message (BaseOverlay::sendToKey's recursive branch,
-// pastry_send_to_key) on the persistent-slice scheduler of persist.hpp; k_pastry_route_acked is the same route
-// under routeMsgAcks, every hop a NextHopCall with its ack.  A hop reads the node's record, its leaf
+// k_pastry_route<ACKS>, which runs one lane per semi-recursive route message (BaseOverlay::sendToKey's recursive
+// branch, pastry_send_to_key) on the persistent-slice scheduler of persist.hpp; its ACKS instantiation is the same
+// route under routeMsgAcks, every hop a NextHopCall with its ack.  A hop reads the node's record, its leaf
 // row and the one table slot the key addresses; the table rows are scanned only for the closer-node fallback and
 // when the first candidate of a numRedundantNodes > 1 answer is refused.  k_pastry_iter runs one lane per
 // IterativeLookup (a LookupCall with its sibling vector, or the one-way message under iterative routing) on the
@@ -167,9 +167,25 @@ __global__ void k_pastry_find_node(PView V, const uint32_t* __restrict__ node, c
 
 constexpr PersistTune KP_TUNE{0.70, 64};
 
+// One lane per semi-recursive route message (BaseOverlay::sendToKey's recursive branch).
+//
+// ACKS: the route under routeMsgAcks (BaseOverlay.cc:1107-1146): every hop is a NextHopCall around the route message,
+// and its receiver sends the NextHopResponse before it forwards (nextHopRpc, 1971-2000), so a forwarder's
+// transmit queue holds the ack when the next call enters it (SimpleNodeEntry.cc:164-194: tx.finished =
+// max(tx.finished, now) + bits / bandwidth) and the call leaves AC.bwAck late.  The source's queue is idle.  A
+// node met twice has drained its queue long before: two hops lie between, each longer than ack plus call.  The
+// sender of the call that arrives now forwarded iff hops > 1, so the lane carries only the largest ack round
+// trip (sendUdpRpcCall to the response's arrival, the wait in the sender's own queue included) and the first
+// hop whose round trip reached rpcUdpTimeout (a tie is a timeout, BaseRpc.cc:191-211).  The route record is the
+// first copy's delivery; the re-route after a timeout (BaseOverlay.cc:1697-1757) is the caller's between batches.
+// A route that fails part-way has sent, and had acknowledged, the calls of the hops it took: hops counts the
+// NextHopCalls sent, each acknowledged by the time the lane ends.  Without ACKS neither AC nor aout is read; the
+// two come last, so the plain instantiation finds its arguments where they were before the kernels were folded.
+template <bool ACKS>
 __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, int hcm, int nred, const K160* __restrict__ qkeys,
                                                       const uint32_t* __restrict__ qsrc, uint64_t nq, uint64_t chunk, PersistDyn dy,
-                                                      ovs_route_out* __restrict__ out, uint32_t* __restrict__ hopseq)
+                                                      ovs_route_out* __restrict__ out, uint32_t* __restrict__ hopseq,
+                                                      PastryAckConsts AC, ovs_pastry_ack_out* __restrict__ aout)
 {
     PersistFeed<KP_TUNE.dyn_chunk> feed(chunk, dy, nq);
     const uint64_t H = (uint64_t)max(hcm, 1);
@@ -181,7 +197,9 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
     uint32_t S = 0, cur = 0, last = NONE;
     double sx = 0, sy = 0;            // the last sender
     int64_t t = 0;
+    [[maybe_unused]] int64_t rttmax = -1;       // ACKS: the largest ack round trip
     int hops = 0;
+    [[maybe_unused]] uint32_t tohop = 0xFF;     // ACKS: the first hop whose ack timed out
     while (true) {
         if (feed.take(active, dy, nq, q)) {
             active = true;
@@ -191,6 +209,7 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
             cur = S;
             last = NONE;
             t = 0; hops = 0;
+            if constexpr (ACKS) { rttmax = -1; tohop = 0xFF; }
         }
         if (!__any(active)) break;
         if (!active) continue;
@@ -199,7 +218,18 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
         const PAns a = pastry_find_node_dev(V, cur, Rc, K, 1);
         uint8_t status = 0xFF;       // 0xFF = still running
         const bool at_src = local;
-        if (!local) t += DC.msgRoute + coord_ns(sx, sy, Rc.x, Rc.y, DC.round);   // sendRouteMessage
+        if (!local) {
+            const int64_t cd = coord_ns(sx, sy, Rc.x, Rc.y, DC.round);
+            if constexpr (ACKS) {
+                const int64_t d = (hops > 1 ? AC.bwAck : 0) + AC.msgCall + cd;      // the call, behind the sender's own ack
+                const int64_t rtt = d + AC.msgAck + cd;                             // the ack leaves an idle queue
+                t += d;
+                rttmax = rtt > rttmax ? rtt : rttmax;
+                if (rtt >= AC.timeout && tohop == 0xFF) tohop = (uint32_t)min(hops - 1, 0xFE);
+            } else {
+                t += DC.msgRoute + cd;   // sendRouteMessage
+            }
+        }
         local = false;
         sx = Rc.x; sy = Rc.y;
         // a forwarded message is delivered on receipt where this node is a sibling (BaseOverlay.cc:907-918); at the
@@ -224,93 +254,14 @@ __global__ __launch_bounds__(256) void k_pastry_route(PView V, DelayConsts DC, i
             o.one_way_hops = (uint8_t)(ok ? hops : 0);
             o.latency_ns = ok ? t : -1;
             out[q] = o;
-            active = false;
-        }
-    }
-}
-
-// The route under routeMsgAcks (BaseOverlay.cc:1107-1146): every hop is a NextHopCall around the route message,
-// and its receiver sends the NextHopResponse before it forwards (nextHopRpc, 1971-2000), so a forwarder's
-// transmit queue holds the ack when the next call enters it (SimpleNodeEntry.cc:164-194: tx.finished =
-// max(tx.finished, now) + bits / bandwidth) and the call leaves AC.bwAck late.  The source's queue is idle.  A
-// node met twice has drained its queue long before: two hops lie between, each longer than ack plus call.  The
-// sender of the call that arrives now forwarded iff hops > 1, so the lane carries only the largest ack round
-// trip (sendUdpRpcCall to the response's arrival, the wait in the sender's own queue included) and the first
-// hop whose round trip reached rpcUdpTimeout (a tie is a timeout, BaseRpc.cc:191-211).  The route record is the
-// first copy's delivery; the re-route after a timeout (BaseOverlay.cc:1697-1757) is the caller's between batches.
-// A route that fails part-way has sent, and had acknowledged, the calls of the hops it took.
-__global__ __launch_bounds__(256) void k_pastry_route_acked(PView V, DelayConsts DC, PastryAckConsts AC, int hcm, int nred,
-                                                            const K160* __restrict__ qkeys, const uint32_t* __restrict__ qsrc,
-                                                            uint64_t nq, uint64_t chunk, PersistDyn dy,
-                                                            ovs_route_out* __restrict__ out, ovs_pastry_ack_out* __restrict__ aout,
-                                                            uint32_t* __restrict__ hopseq)
-{
-    PersistFeed<KP_TUNE.dyn_chunk> feed(chunk, dy, nq);
-    const uint64_t H = (uint64_t)max(hcm, 1);
-
-    bool active = false, local = true;
-    uint64_t q = 0;
-    K160 K;
-    K.w[0] = K.w[1] = K.w[2] = K.w[3] = K.w[4] = 0;
-    uint32_t S = 0, cur = 0, last = NONE;
-    double sx = 0, sy = 0;            // the last sender
-    int64_t t = 0, rttmax = -1;
-    int hops = 0;                     // NextHopCalls sent, each acknowledged by the time the lane ends
-    uint32_t tohop = 0xFF;
-    while (true) {
-        if (feed.take(active, dy, nq, q)) {
-            active = true;
-            local = true;
-            K = qkeys[q];
-            S = qsrc[q];
-            cur = S;
-            last = NONE;
-            t = 0; hops = 0;
-            rttmax = -1; tohop = 0xFF;
-        }
-        if (!__any(active)) break;
-        if (!active) continue;
-
-        const PRec Rc = load_prec(V.rec, cur);
-        const PAns a = pastry_find_node_dev(V, cur, Rc, K, 1);
-        uint8_t status = 0xFF;       // 0xFF = still running
-        const bool at_src = local;
-        if (!local) {
-            const int64_t cd = coord_ns(sx, sy, Rc.x, Rc.y, DC.round);
-            const int64_t d = (hops > 1 ? AC.bwAck : 0) + AC.msgCall + cd;      // the call, behind the sender's own ack
-            const int64_t rtt = d + AC.msgAck + cd;                             // the ack leaves an idle queue
-            t += d;
-            rttmax = rtt > rttmax ? rtt : rttmax;
-            if (rtt >= AC.timeout && tohop == 0xFF) tohop = (uint32_t)min(hops - 1, 0xFE);
-        }
-        local = false;
-        sx = Rc.x; sy = Rc.y;
-        if (!at_src && a.closest) status = OVS_LOOKUP_OK;
-        else {
-            const PStep st = pastry_send_to_key(V, cur, Rc, K, a, hops, hcm, nred, last, S);
-            status = st.status;
-            if (status == PSTEP_FORWARD) {
-                if (hopseq) hopseq[q * H + (uint64_t)hops] = st.next;   // hops < hcm here
-                ++hops;
-                last = cur;
-                cur = st.next;
-            }
-        }
-        if (status != 0xFF) {
-            ovs_route_out o;
-            const bool ok = status == OVS_LOOKUP_OK;
-            o.responsible = ok ? cur : NONE;
-            o.hops = (uint16_t)(ok ? hops : 0);
-            o.status = status;
-            o.one_way_hops = (uint8_t)(ok ? hops : 0);
-            o.latency_ns = ok ? t : -1;
-            out[q] = o;
-            if (aout) {
-                ovs_pastry_ack_out ao{};
-                ao.max_ack_rtt_ns = rttmax;
-                ao.acks = (uint16_t)hops;
-                ao.timeout_hop = (uint8_t)tohop;
-                aout[q] = ao;
+            if constexpr (ACKS) {
+                if (aout) {
+                    ovs_pastry_ack_out ao{};
+                    ao.max_ack_rtt_ns = rttmax;
+                    ao.acks = (uint16_t)hops;
+                    ao.timeout_hop = (uint8_t)tohop;
+                    aout[q] = ao;
+                }
             }
             active = false;
         }
@@ -632,29 +583,19 @@ hipError_t pastry_find_node(const PastryTables& t, const uint32_t* node, const K
     return hipGetLastError();
 }
 
-hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCountMax, int recNumRedundantNodes, const K160* keys,
-                        const uint32_t* src, uint64_t nq, ovs_route_out* out, uint32_t* hopseq, int num_cu, hipStream_t st,
-                        unsigned long long* dyn)
+hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, const PastryAckConsts* AC, int hopCountMax,
+                        int recNumRedundantNodes, const K160* keys, const uint32_t* src, uint64_t nq, ovs_route_out* out,
+                        ovs_pastry_ack_out* ack_out, uint32_t* hopseq, int num_cu, hipStream_t st, unsigned long long* dyn)
 {
     if (nq == 0) return hipSuccess;
-    using K = PersistKernel<k_pastry_route>;
-    const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
-    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
-    hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, recNumRedundantNodes, keys,
-                       src, nq, pl.chunk, dy, out, hopseq);
-    return hipGetLastError();
-}
-
-hipError_t pastry_route_acked(const PastryTables& t, const DelayConsts& DC, const PastryAckConsts& AC, int hopCountMax,
-                              int recNumRedundantNodes, const K160* keys, const uint32_t* src, uint64_t nq, ovs_route_out* out,
-                              ovs_pastry_ack_out* ack_out, uint32_t* hopseq, int num_cu, hipStream_t st, unsigned long long* dyn)
-{
-    if (nq == 0) return hipSuccess;
-    using K = PersistKernel<k_pastry_route_acked>;
-    const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
-    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
-    hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, AC, hopCountMax, recNumRedundantNodes,
-                       keys, src, nq, pl.chunk, dy, out, ack_out, hopseq);
+    if (!AC && ack_out) return hipErrorInvalidValue;
+    auto launch = [&](auto k) {
+        using K = decltype(k);
+        const PersistLaunch pl = persist_launch<K::fn>(nq, num_cu, dyn, KP_TUNE);
+        hipLaunchKernelGGL(K::fn, dim3(pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, recNumRedundantNodes, keys, src, nq,
+                           pl.chunk, pl.dy, out, hopseq, AC ? *AC : PastryAckConsts{}, ack_out);
+    };
+    if (AC) launch(PersistKernel<k_pastry_route<true>>{}); else launch(PersistKernel<k_pastry_route<false>>{});
     return hipGetLastError();
 }
 
@@ -682,10 +623,9 @@ hipError_t pastry_iter(const PastryTables& t, const DelayConsts& DC, int hopCoun
     if (!hopseq || hopCountMax < 1 || numSiblings < 1 || numSiblings > t.sh.L / 2 || !rout == !lout || (rout && numSiblings != 1))
         return hipErrorInvalidValue;
     using K = PersistKernel<k_pastry_iter>;
-    const PersistPlan pl = persist_plan(nq, persist_waves<K::fn>(num_cu), dyn != nullptr, KP_TUNE);
-    const PersistDyn dy{pl.dyn ? dyn : nullptr, pl.dyn_from};
-    hipLaunchKernelGGL(K::fn, dim3((unsigned)pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, numSiblings, keys, src, nq,
-                       pl.chunk, dy, rout, lout, siblings, hopseq, rpcs);
+    const PersistLaunch pl = persist_launch<K::fn>(nq, num_cu, dyn, KP_TUNE);
+    hipLaunchKernelGGL(K::fn, dim3(pl.blocks), dim3(256), 0, st, make_view(t), DC, hopCountMax, numSiblings, keys, src, nq, pl.chunk,
+                       pl.dy, rout, lout, siblings, hopseq, rpcs);
     return hipGetLastError();
 }
 

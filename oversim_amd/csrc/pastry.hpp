@@ -55,15 +55,12 @@ hipError_t pastry_slot_nodes(const PastryTables& t, uint32_t* dleaf, uint32_t* d
 hipError_t pastry_find_node(const PastryTables& t, const uint32_t* node, const K160* keys, uint64_t nq, int numRedundantNodes,
                             int numSiblings, uint32_t* out_nodes, uint32_t max_out, uint8_t* count, uint8_t* sib,
                             uint8_t* status, hipStream_t st);
-// batched semi-recursive one-way routes; hopseq (nq * max(hopCountMax, 1), preset to NONE) or nullptr
-hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, int hopCountMax, int recNumRedundantNodes, const K160* keys,
-                        const uint32_t* src, uint64_t nq, ovs_route_out* out, uint32_t* hopseq, int num_cu, hipStream_t st,
-                        unsigned long long* dyn = nullptr);
-// the same routes under routeMsgAcks (k_pastry_route_acked); ack_out may be nullptr
-hipError_t pastry_route_acked(const PastryTables& t, const DelayConsts& DC, const PastryAckConsts& AC, int hopCountMax,
-                              int recNumRedundantNodes, const K160* keys, const uint32_t* src, uint64_t nq, ovs_route_out* out,
-                              ovs_pastry_ack_out* ack_out, uint32_t* hopseq, int num_cu, hipStream_t st,
-                              unsigned long long* dyn = nullptr);
+// batched semi-recursive one-way routes (k_pastry_route<ACKS>); hopseq (nq * max(hopCountMax, 1), preset to NONE) or
+// nullptr.  AC nullptr: plain routes, and ack_out must be nullptr too; else the same routes under routeMsgAcks, with
+// their ack records where ack_out is given
+hipError_t pastry_route(const PastryTables& t, const DelayConsts& DC, const PastryAckConsts* AC, int hopCountMax,
+                        int recNumRedundantNodes, const K160* keys, const uint32_t* src, uint64_t nq, ovs_route_out* out,
+                        ovs_pastry_ack_out* ack_out, uint32_t* hopseq, int num_cu, hipStream_t st, unsigned long long* dyn = nullptr);
 // ack records of routes that sent no NextHopCall (routeMsgAcks = false)
 hipError_t pastry_acks_none(uint64_t nq, ovs_pastry_ack_out* ack_out, hipStream_t st);
 // ack records of pastry_iter's one-way routes: one NextHopCall src -> rout.responsible where the two differ

@@ -1,7 +1,7 @@
 // persist.hpp -- the persistent-slice scheduler shared by the lane-refill route kernels: K1
 // (k_chord_lanes, chord.hip), K2 (k_kad_route, kad_route.hip), K2x (k_kad_refresh, kad_refresh.hip),
-// K3 (k_koorde_route, koorde.hip), K4 (k_broose_route, broose.hip) and the two Pastry kernels
-// (k_pastry_route, k_pastry_iter, pastry.hip).
+// K3 (k_koorde_route, koorde.hip), K4 (k_broose_route, broose.hip) and the Pastry kernels
+// (k_pastry_route<ACKS>: plain routes and routes under routeMsgAcks; k_pastry_iter; pastry.hip).
 //
 // Each launches an occupancy-sized persistent grid and gives every wave one contiguous static slice
 // of the batch; a lane whose lookup ended takes the wave's next one by ballot + popcount (the
@@ -13,7 +13,7 @@
 //
 // The plan (persist_plan) is plain C++: it compiles without a HIP compiler
 // (tests/persist_plan_driver.cpp).  The occupancy query, the refill and the tail census need one
-// (__HIPCC__).  On the device the refill is stated once, PersistFeed<CH>::take: K4 and the two Pastry
+// (__HIPCC__).  On the device the refill is stated once, PersistFeed<CH>::take: K4 and the Pastry
 // kernels, which are untuned, run it.  K1, K2, K2x and K3 keep cursor / end / more / lt_mask as
 // locals of their own loops and share only the claim of the next dynamic chunk, persist_claim_chunk:
 // as members of a shared object these compiled to different register allocations (K1's shard step
@@ -122,6 +122,21 @@ struct PersistDyn {
     unsigned long long* ctr;
     uint64_t from;
 };
+
+// What a launcher whose grid is the kernel's occupancy hands to hipLaunchKernelGGL (K3, K4, the Pastry
+// kernels): the plan of nq lookups over the instantiation's resident waves, with the dynamic tail
+// where the caller brings a zeroed counter and the plan uses it
+struct PersistLaunch {
+    unsigned blocks;
+    uint64_t chunk;
+    PersistDyn dy;
+};
+template <auto Kernel>
+PersistLaunch persist_launch(uint64_t nq, int num_cu, unsigned long long* dyn, PersistTune t)
+{
+    const PersistPlan pl = persist_plan(nq, persist_waves<Kernel>(num_cu), dyn != nullptr, t);
+    return {(unsigned)pl.blocks, pl.chunk, PersistDyn{pl.dyn ? dyn : nullptr, pl.dyn_from}};
+}
 
 // A wave's feed of lookups: its static slice [wave * chunk, (wave + 1) * chunk) cut at the end of the
 // static region, then dynamic chunks of CH lookups while the batch lasts.  A kernel's loop head reads

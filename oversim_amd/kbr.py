@@ -922,23 +922,32 @@ class KbrEngine:
                   "ovs_pastry_find_node_batch")
         return out, cnt, sib, st
 
-    def pastry_lookup(self, keys, src, record_hops: bool = False) -> dict:
-        """Batched semi-recursive one-way routes on a Pastry context (ovs_pastry_route_batch).  Returns numpy
-        arrays by field, as lookup()."""
+    def _pastry_one_way(self, name: str, takes: tuple, keys, src, record_hops: bool = False, ack_records: bool = False,
+                        out_dtype=ROUTE_OUT_DTYPE) -> dict:
+        """What the Pastry one-way wrappers share: keys and src as arrays of one length, the out records, the
+        optional ack records and hop rows, the call `name`, which takes the buffers `takes` names in that order,
+        and the records unpacked by field."""
         keys = keys_array(keys)
         src = np.ascontiguousarray(src, dtype=np.uint32)
         n = len(keys)
         if len(src) != n:
             raise ValueError("keys and src differ in length")
-        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
-        H = max(self.get_params().hopCountMax, 1)
-        hop = np.empty((n, H), dtype=np.uint32) if record_hops else None
-        self._chk(self._L.ovs_pastry_route_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), _ptr(hop), 0, None),
-                  "ovs_pastry_route_batch")
-        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
+        out = np.empty(n, dtype=out_dtype)
+        ack = np.empty(n, dtype=PASTRY_ACK_OUT_DTYPE) if ack_records else None
+        hop = np.empty((n, max(self.get_params().hopCountMax, 1)), dtype=np.uint32) if record_hops else None
+        bufs = {"out": out, "ack": ack, "hop": hop}
+        self._chk(getattr(self._L, name)(self._h, _ptr(keys), _ptr(src), n, *(_ptr(bufs[b]) for b in takes), 0, None), name)
+        res = {f: out[f].copy() for f in out_dtype.names}
+        if ack is not None:
+            res.update({f: ack[f].copy() for f in PASTRY_ACK_OUT_DTYPE.names})
         if hop is not None:
             res["hop_seq"] = hop
         return res
+
+    def pastry_lookup(self, keys, src, record_hops: bool = False) -> dict:
+        """Batched semi-recursive one-way routes on a Pastry context (ovs_pastry_route_batch).  Returns numpy
+        arrays by field, as lookup()."""
+        return self._pastry_one_way("ovs_pastry_route_batch", ("out", "hop"), keys, src, record_hops)
 
     def pastry_lookup_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
         """Device-resident batch (async on `stream`)."""
@@ -981,19 +990,7 @@ class KbrEngine:
     def pastry_iterative_lookup(self, keys, src, record_hops: bool = False) -> dict:
         """Batched KBRTestApp one-way routes under iterative routing on a Pastry context
         (ovs_pastry_iterative_route_batch; params.routingType = 0).  Returns numpy arrays by field, as lookup()."""
-        keys = keys_array(keys)
-        src = np.ascontiguousarray(src, dtype=np.uint32)
-        n = len(keys)
-        if len(src) != n:
-            raise ValueError("keys and src differ in length")
-        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
-        hop = np.empty((n, max(self.get_params().hopCountMax, 1)), dtype=np.uint32) if record_hops else None
-        self._chk(self._L.ovs_pastry_iterative_route_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), _ptr(hop), 0, None),
-                  "ovs_pastry_iterative_route_batch")
-        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
-        if hop is not None:
-            res["hop_seq"] = hop
-        return res
+        return self._pastry_one_way("ovs_pastry_iterative_route_batch", ("out", "hop"), keys, src, record_hops)
 
     def pastry_iterative_lookup_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
         """Device-resident batch (async on `stream`)."""
@@ -1008,22 +1005,7 @@ class KbrEngine:
         final message goes as one NextHopCall.  Returns the route fields as lookup() and, per route, acks (the
         NextHopCalls sent), max_ack_rtt_ns (-1 without one) and timeout_hop (the first hop whose ack round trip
         reached rpcUdpTimeout, 0xFF = none); ack_records=False passes no ack buffer."""
-        keys = keys_array(keys)
-        src = np.ascontiguousarray(src, dtype=np.uint32)
-        n = len(keys)
-        if len(src) != n:
-            raise ValueError("keys and src differ in length")
-        out = np.empty(n, dtype=ROUTE_OUT_DTYPE)
-        ack = np.empty(n, dtype=PASTRY_ACK_OUT_DTYPE) if ack_records else None
-        hop = np.empty((n, max(self.get_params().hopCountMax, 1)), dtype=np.uint32) if record_hops else None
-        self._chk(self._L.ovs_pastry_acked_route_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), _ptr(ack), _ptr(hop), 0,
-                                                       None), "ovs_pastry_acked_route_batch")
-        res = {f: out[f].copy() for f in ROUTE_OUT_DTYPE.names}
-        if ack is not None:
-            res.update({f: ack[f].copy() for f in PASTRY_ACK_OUT_DTYPE.names})
-        if hop is not None:
-            res["hop_seq"] = hop
-        return res
+        return self._pastry_one_way("ovs_pastry_acked_route_batch", ("out", "ack", "hop"), keys, src, record_hops, ack_records)
 
     def pastry_acked_lookup_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, ack_out_ptr: int | None = None,
                                    stream: int | None = None):
@@ -1036,14 +1018,7 @@ class KbrEngine:
     def pastry_rpc(self, keys, src) -> dict:
         """Batched routed KbrTestCall round trips on a Pastry context (ovs_pastry_rpc_batch; KBRTestApp with
         kbrRpcTest, semi-recursive routing, either routeMsgAcks).  Returns the ovs_rpc_out fields as rpcCall()."""
-        keys = keys_array(keys)
-        src = np.ascontiguousarray(src, dtype=np.uint32)
-        n = len(keys)
-        if len(src) != n:
-            raise ValueError("keys and src differ in length")
-        out = np.empty(n, dtype=RPC_OUT_DTYPE)
-        self._chk(self._L.ovs_pastry_rpc_batch(self._h, _ptr(keys), _ptr(src), n, _ptr(out), 0, None), "ovs_pastry_rpc_batch")
-        return {f: out[f].copy() for f in RPC_OUT_DTYPE.names}
+        return self._pastry_one_way("ovs_pastry_rpc_batch", ("out",), keys, src, out_dtype=RPC_OUT_DTYPE)
 
     def pastry_rpc_device(self, keys_ptr: int, src_ptr: int, n: int, out_ptr: int, stream: int | None = None):
         """Device-resident RPC batch (async on `stream`): out n ovs_rpc_out."""

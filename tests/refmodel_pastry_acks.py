@@ -1,5 +1,5 @@
 """Pastry routes with per-hop acks (routeMsgAcks = true, default.ini:245) and KBRTestApp's RPC test on them,
-replayed event by event on top of refmodel_pastry: the checker of k_pastry_route_acked (oversim_amd/csrc/pastry.hip)
+replayed event by event on top of refmodel_pastry: the checker of k_pastry_route<true> (oversim_amd/csrc/pastry.hip)
 and of ovs_pastry_rpc_batch.
 
 Test infrastructure only.  The routing decisions are refmodel_pastry.PastryNet.route's (findNode and the recursive

@@ -1,4 +1,4 @@
-"""Pastry routes with per-hop acks and KBRTestApp's RPC test on the GPU (k_pastry_route_acked, oversim_amd/csrc/
+"""Pastry routes with per-hop acks and KBRTestApp's RPC test on the GPU (k_pastry_route<true>, oversim_amd/csrc/
 pastry.hip; ovs_pastry_acked_route_batch, ovs_pastry_rpc_batch) against the event replay of
 tests/refmodel_pastry_acks.py, bit for bit on every field: route record, hop sequence, ack record, RPC record."""
 from __future__ import annotations
@@ -119,6 +119,23 @@ def test_without_acks_equals_the_plain_route(engine: KbrEngine):
     assert (got["acks"] == 0).all() and (got["max_ack_rtt_ns"] == -1).all() and (got["timeout_hop"] == 0xFF).all()
     want = RA.routes(m, keys, src, acks=False)
     _assert(got, want, ROUTE + ACK + ("hop_seq",), "routeMsgAcks=0 model")
+
+
+@pytest.mark.parametrize("hcm", [50, 3])
+@pytest.mark.parametrize("n", [9, 1000])
+def test_acked_and_plain_instantiations_share_their_paths(engine: KbrEngine, n, hcm):
+    """k_pastry_route<true> (routeMsgAcks = 1 through pastry_acked_lookup) and k_pastry_route<false> (routeMsgAcks = 0
+    through pastry_lookup) on the same tables and batch take the same paths to the same ends; only latency_ns, which
+    the acks lengthen by design, is left out.  hopCountMax = 3 cuts routes of the 1000-node network at the limit."""
+    keys, src = _batch(n)
+    _load(engine, n, acks=1, hopCountMax=hcm)
+    acked = engine.pastry_acked_lookup(keys, src, record_hops=True)
+    _load(engine, n, acks=0, hopCountMax=hcm)
+    plain = engine.pastry_lookup(keys, src, record_hops=True)
+    _assert(acked, plain, ("responsible", "hops", "status", "one_way_hops", "hop_seq"), f"n={n} hopCountMax={hcm}")
+    assert (acked["acks"] > 0).any()                              # the acked instantiation ran
+    if n == 1000 and hcm == 3:
+        assert (plain["status"] == RP.HOPMAX).any()
 
 
 @pytest.mark.parametrize("acks", [1, 0])

@@ -7,11 +7,11 @@ loaded once without acks and once with them (routeMsgAcks is a property of the c
 random sources on device pointers.  After one warm-up of each, every repetition alternates three calls un-profiled,
 each timed from launch to the stream's synchronisation:
 
-  plain   ovs_pastry_route_batch, routeMsgAcks = 0        (k_pastry_route)
-  acked   ovs_pastry_acked_route_batch with ack records    (k_pastry_route_acked)
-  rpc     ovs_pastry_rpc_batch, routeMsgAcks = 1           (k_pastry_route_acked without ack records + k_rpc_finish)
+  plain   ovs_pastry_route_batch, routeMsgAcks = 0        (k_pastry_route<false>)
+  acked   ovs_pastry_acked_route_batch with ack records    (k_pastry_route<true>)
+  rpc     ovs_pastry_rpc_batch, routeMsgAcks = 1           (k_pastry_route<true> without ack records + k_rpc_finish)
 
-Writes medians, spread (max - min), hops/s and the ratios to --out as text.  The acked kernel reads the same bytes a
+Writes medians, spread (max - min), hops/s and the ratios to --out as text.  The acked instantiation reads the same bytes a
 hop as the plain one (64 B record + 24 B x numberOfLeaves leaf row + one 24 B slot); it writes 16 B more a route.
 """
 from __future__ import annotations
