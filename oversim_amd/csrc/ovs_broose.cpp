@@ -83,6 +83,11 @@ ovs_status ovs_broose_load(ovs_ctx* c, const ovs_broose_params* bp, const ovs_ke
                            uint32_t flags)
 {
     if (!c || !bp || !ids || !xy) return OVS_EINVAL;
+    {
+        // a shape outside the implemented ranges is refused before the frame drops the loaded network
+        std::string err;
+        if (!broose_shape_ok(shape_of(*bp), &err)) return fail(c, OVS_ENOTSUP, "Broose: " + err);
+    }
     LoadFrame L(c, OVS_OVERLAY_BROOSE, "Broose");
     if (L.st) return L.st;
     BrooseShape sh;

@@ -754,15 +754,15 @@ class KbrEngine:
         params.overlay must be OVERLAY_BROOSE."""
         ids = keys_array(ids)
         xy = np.ascontiguousarray(xy, dtype=np.float64)
-        self._bp = bp if bp is not None else BrooseParams.default()
-        self._chk(self._L.ovs_broose_load(self._h, C.byref(self._bp), _ptr(ids), len(ids), _ptr(xy), 0), "ovs_broose_load")
-        self.n, self.overlay = len(ids), OVERLAY_BROOSE
+        bp = bp if bp is not None else BrooseParams.default()
+        self._chk(self._L.ovs_broose_load(self._h, C.byref(bp), _ptr(ids), len(ids), _ptr(xy), 0), "ovs_broose_load")
+        self._bp, self.n, self.overlay = bp, len(ids), OVERLAY_BROOSE      # a refused load leaves the loaded shape
 
     def broose_load_device(self, ids_ptr: int, xy_ptr: int, n: int, bp: "BrooseParams | None" = None):
-        self._bp = bp if bp is not None else BrooseParams.default()
-        self._chk(self._L.ovs_broose_load(self._h, C.byref(self._bp), C.c_void_p(ids_ptr), n, C.c_void_p(xy_ptr),
+        bp = bp if bp is not None else BrooseParams.default()
+        self._chk(self._L.ovs_broose_load(self._h, C.byref(bp), C.c_void_p(ids_ptr), n, C.c_void_p(xy_ptr),
                                           DEVICE_PTRS), "ovs_broose_load")
-        self.n, self.overlay = n, OVERLAY_BROOSE
+        self._bp, self.n, self.overlay = bp, n, OVERLAY_BROOSE
 
     def broose_load_tables(self, ids, xy, row_off, row_nodes, bp: "BrooseParams | None" = None):
         """Explicit Broose buckets in CSR form (ovs_broose_load_tables): row r of node v =
@@ -771,14 +771,14 @@ class KbrEngine:
         xy = np.ascontiguousarray(xy, dtype=np.float64)
         off = np.ascontiguousarray(row_off, dtype=np.uint64)
         nd = np.ascontiguousarray(row_nodes, dtype=np.uint32)
-        self._bp = bp if bp is not None else BrooseParams.default()
-        if len(off) != len(ids) * self._bp.num_rows() + 1:
+        bp = bp if bp is not None else BrooseParams.default()
+        if len(off) != len(ids) * bp.num_rows() + 1:
             raise ValueError("row_off must have n * rows + 1 entries")
         if len(nd) < int(off[-1]):
             raise ValueError("row_nodes is shorter than row_off[-1]")
-        self._chk(self._L.ovs_broose_load_tables(self._h, C.byref(self._bp), _ptr(ids), len(ids), _ptr(xy), _ptr(off),
+        self._chk(self._L.ovs_broose_load_tables(self._h, C.byref(bp), _ptr(ids), len(ids), _ptr(xy), _ptr(off),
                                                  _ptr(nd) if len(nd) else None, 0), "ovs_broose_load_tables")
-        self.n, self.overlay = len(ids), OVERLAY_BROOSE
+        self._bp, self.n, self.overlay = bp, len(ids), OVERLAY_BROOSE
 
     def broose_export(self):
         """(row_off (n * rows + 1), row_nodes) of the loaded Broose buckets."""

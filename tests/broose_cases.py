@@ -62,10 +62,12 @@ def assert_routes_equal(got: dict, want: dict, H: int):
             assert list(row[:len(seq)]) == seq and np.all(row[len(seq):] == NONE), i
 
 
-def find_node_calls(m: RB.BrooseNet, total: int, seed: int):
+def find_node_calls(m: RB.BrooseNet, total: int, seed: int, direct=(), key_pool=None, node_pool=None):
     """`total` findNode calls (node, key, incoming extension or None, direction flag) with their class names:
     sibling, first_left, first_right, mid_left, mid_right, brother, loop, broken -- the mid-route and brother
-    calls are the ones the model's own lookups send."""
+    calls are the ones the model's own lookups send.  Any model serves.  direct: calls (node, key, extension or
+    None, direction) that come first; key_pool (ints) / node_pool: where every second chain takes its key / its
+    first node from instead of a uniform draw."""
     rng = np.random.default_rng(seed)
     calls = []
 
@@ -91,10 +93,18 @@ def find_node_calls(m: RB.BrooseNet, total: int, seed: int):
         calls.append((v, k, e, right, cls, res, msg.get("ext")))
         return None if sib else (res[0], msg["ext"])
 
+    for v, k, e, right in direct:
+        add(int(v), int(k), e, bool(right))
+    chains = 0
     while len(calls) < total - 200:
         # one chain: the calls of a lookup, each fed the extension the previous response carried
         k = RB.to_int(W.random_keys(1, rng)[0])
         v, e, right = int(rng.integers(0, m.n)), None, bool(rng.integers(0, 2))
+        chains += 1
+        if key_pool is not None and chains % 2:
+            k = int(key_pool[int(rng.integers(0, len(key_pool)))])
+        if node_pool is not None and chains % 4 < 2:
+            v = int(node_pool[int(rng.integers(0, len(node_pool)))])
         for _ in range(40):
             nxt = add(v, k, e, right)
             if nxt is None or nxt[0] == v:

@@ -219,3 +219,88 @@ def test_table_validation_driver(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "ok" in r.stdout
+
+
+# ---------------------------------------------------------------------------
+# the crafted rings of tests/broose_rings.py: what tests/test_gpu_broose_deep.py relies on, asserted here so that
+# it cannot pass vacuously
+
+import broose_rings as BR  # noqa: E402
+
+CRAFTED = ([(name, BR.DEFAULT_SHAPE) for name in BR.RINGS] + [(BR.SHAPE_RING, sh) for sh in BR.SHAPES]
+           + [(name, sh) for name in BR.PAIR_RINGS for sh in BR.PAIR_SHAPES])
+
+
+@pytest.mark.parametrize("name,shape", CRAFTED)
+def test_crafted_rows_add_fast_and_brute_agree(name, shape):
+    a, f = BR.model(name, shape), BR.model(name, shape, build="fast")
+    for v in range(a.n):
+        want = [closest_brute(a.ids, bk.key, bk.max_size) for bk in a.buckets[v]]
+        assert a.rows(v) == want, (v, "add")
+        assert f.rows(v) == want, (v, "trie descent")
+
+
+@pytest.mark.parametrize("name", BR.RINGS)
+def test_crafted_ring_census(name, capsys):
+    net, runs, feed = BR.ring(name)
+    c = BR.census_of(name)
+    t = BR.census_of(name, timeout=True)
+    with capsys.disabled():
+        print(f"\n{name}: n={len(net.ids)} ties={c['tie_rows']} split_lt={c['split_lt']} dist>31={c['dist_gt31']} "
+              f"maxdist={max(c['dist_hist'])} sib(top32/eq/+1/-1)={c['sib_top32']}/{c['sib_eq']}/{c['sib_above']}/{c['sib_below']} "
+              f"status={dict(sorted(c['status'].items()))} | timeout {BR.timeout_between(BR.model(name))}: "
+              f"status={dict(sorted(t['status'].items()))} retries={t['retries']} low={t['retries_low']}")
+    assert c["tie_rows"] > 20
+    assert c["split_lt"][BR.split_limit(name)] > 20
+    assert c["sib_top32"] > 50 and min(c["sib_eq"], c["sib_above"], c["sib_below"]) > 5
+    assert c["status"].get(0, 0) > 100
+    assert t["status"].get(2, 0) > 20 and t["retries"] > 20
+    if name in BR.RUN_RINGS:
+        # the feeders: rBucket[0] inside a run, longestPrefix from run members alone
+        assert c["dist_gt31"] >= 3 and max(c["dist_hist"]) >= 160 - BR.low_bits_of(name)
+        assert all(BR.model(name).distance_estimate(v) > 31 for v in feed[3:6])
+        assert c["status"].get(4, 0) > 0 and c["status"].get(5, 0) > 0
+
+
+def test_crafted_census_over_all_rings():
+    # the source's second candidate after a first-hop timeout, picked among entries that agree in the top word
+    assert sum(BR.census_of(name, timeout=True)["retries_low"] for name in BR.RINGS) > 50
+    # one ring splits at bit 31, one at bit 32, one at bit 63, one at bit 95 (the first two members of a run)
+    for name, bit in (("lb32", 31), ("lb33", 32), ("lb64", 63), ("lb96", 95)):
+        ids, run = BR.model(name).ids, BR.ring(name)[1][0]
+        assert (ids[run[0]] ^ ids[run[-1]]).bit_length() - 1 == bit
+    assert BR.census_of("lb5", hop_max=3)["status"].get(3, 0) > 20
+    ids, run = BR.model("edge").ids, BR.ring("edge")[1][0]
+    assert ids[0] == 0 and ids[-1] == RB.M - 1 and ids[run[0]] < 1 << 159 <= ids[run[-1]]
+
+
+@pytest.mark.parametrize("shape", BR.SHAPES)
+def test_crafted_shape_census(shape, capsys):
+    c = BR.census_of(BR.SHAPE_RING, shape)
+    with capsys.disabled():
+        print(f"\n{BR.SHAPE_RING} {shape}: ties={c['tie_rows']} split_lt={c['split_lt']} dist>31={c['dist_gt31']} "
+              f"maxdist={max(c['dist_hist'])} status={dict(sorted(c['status'].items()))}")
+    assert c["tie_rows"] > 20 and c["split_lt"][64] > 20
+    assert c["status"].get(0, 0) > 0 and c["status"].get(4, 0) > 0
+    if shape[0] == 1:
+        assert c["status"][4] > 400                     # bucketSize = 1: almost every route ends without a next hop
+
+
+@pytest.mark.parametrize("name", BR.PAIR_RINGS)
+def test_pair_rings_reach_the_distance_cap(name, capsys):
+    """ids X, X ^ 1 (and X ^ 2): longestPrefix 159 (158), a raw estimate of 160 + userDist before the rounding to
+    shiftingBits.  The `dist > KEYBITS` cap is taken wherever the rounded estimate passes 160: shiftingBits 3 (162 ->
+    159, on the pair) and userDist 2.  (shiftingBits 2, userDist 0) gives exactly 160 and is not capped; in the triple
+    X ^ 2 is always the closest or the farthest entry, longestPrefix is 158 and shiftingBits 3 leaves 159 as it is."""
+    for k, kr, sb, ud in BR.PAIR_SHAPES:
+        m = BR.model(name, (k, kr, sb, ud))
+        c = BR.census_of(name, (k, kr, sb, ud))
+        with capsys.disabled():
+            print(f"\n{name} sb={sb} userDist={ud}: dist={c['dist_hist']} capped={c['dist_cap']} status={dict(sorted(c['status'].items()))}")
+        assert set(c["dist_hist"]) == {160 - 160 % sb}
+        if ud == 2 or (sb == 3 and name == "pair2"):
+            assert c["dist_cap"] == m.n
+        # bucketSize = 1: a key is a sibling's only at its own node, so the estimate is used -- right-shifting rounds
+        # from step 160 / 159, and a broken left-shifting start
+        assert c["status"].get(0, 0) > 0 and c["status"].get(5, 0) > 0
+        assert any(len(m.lookup(*q)["hop_seq"]) > 0 for q in zip(*BR.batch(name, (k, kr, sb, ud))))
